@@ -2,6 +2,7 @@
 """Benchmark of the denoiser hot path on MI355X (contract: see the task brief / DESIGN.md §Measurement).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N --steps K --warmup W        # starts the N ranks itself (torchrun children)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
@@ -514,6 +515,45 @@ def forward_target_shape(tr, device, B=64, L=8192):
             "frames_per_s": round(B * L / dt, 0)}
 
 
+DUMP_SAMPLE = 1 << 20         # parameter positions drawn by --dump-outputs (the full arrays are 187.5 MB each in fp32)
+DUMP_SEED = 20241015
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs DIR: what the timed path handed back in its last step, as float32 .npy files under DIR — the loss and the
+    terms the step logs, and the same fixed, seeded sample of positions from the updated weights, from that step's gradients and
+    from the EMA weights (all of them when the model has no more than DUMP_SAMPLE).  Positions index the parameters flattened in
+    named_parameters() order (independent of the arena's layout) and are written as sample_index.npy (float64, exact); numpy's
+    legacy RandomState draws them, whose stream numpy keeps fixed across versions.  About 20 MB in all.
+    The inputs (weights, batch, noise draws) repeat exactly under the same arguments; the outputs repeat to fp32-atomic order by
+    default (1.7e-2 rel-L2 in the gradients after 25 bf16 steps at configs[1]) and bit for bit under OD_DETERMINISTIC=1 (osu_dreamer_amd/det.py)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+    for k in ("loss", "osl", "del", "u_mape"):
+        save(k, tr._logged[f"train/{k}"].detach().float().cpu().numpy())
+    named = list(tr.diffusion.named_parameters())
+    total = sum(p.numel() for _, p in named)
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+    idx_dev = torch.from_numpy(idx).to(named[0][1].device)
+    ema = dict(tr.diffusion_ema.module.named_parameters())
+
+    def sample(tensors):
+        return torch.cat([t.detach().reshape(-1) for t in tensors]).float()[idx_dev].cpu().numpy()
+
+    assert all(p.grad is not None for _, p in named), "no gradient attached after the step"
+    save("sample_index", idx.astype(np.float64))
+    save("params", sample([p for _, p in named]))
+    save("grads", sample([p.grad for _, p in named]))
+    save("ema_params", sample([ema[n] for n, _ in named]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -526,6 +566,9 @@ def main():
                     help="f16: the attention core on IEEE-half operands (BASELINE configs[4] 'attention in fp16'; bf16 compute around it)")
     ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline / sampler legs")
     ap.add_argument("--cpu-frames", type=int, default=2048, help="length of the CPU baseline's batch-1 sample (8192 = the bench's own L: minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss terms; a seeded sample of weights, gradients, "
+                         "EMA weights) as DIR/<name>.npy, rank 0 only; bit-identical between runs under OD_DETERMINISTIC=1")
     args = ap.parse_args()
 
     # --gpus N: one process per GPU.  Outside a torchrun job this process only starts the N ranks (as children,
@@ -604,6 +647,8 @@ def main():
         per_rank = torch.stack(allr).cpu()
         dt = float(per_rank[:, 0].max()) * args.steps / 1e3
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     alone = allreduce_alone(reducer, device) if ddp else None        # every rank: a collective
 
     if rank == 0:
