@@ -552,8 +552,14 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_fused_kernel(const bf16_t* _
             //     c = 1 + (launches * G + generation) * nkb + key block        (G = generations of this slot per launch; a zero-filled slot is "write 0")
             // and a key block proceeds only when the tile carries c - 1: its predecessor's write — or, for the first key block, the LAST block's marker
             // of the slot's previous user, i.e. that user has read what is about to be overwritten.  Every 16-byte piece (one lane of one load /
-            // store instruction: the unit the memory system moves) carries c mod 4096, three bits in the lowest mantissa bits of each of its four
-            // dwords (2^-20 relative per hop: far below the bf16 result's own rounding).  A piece is accepted only with exactly that number: the
+            // store instruction: the unit the memory system moves) carries the number.  Packed form (FB_PACK, the default): c mod 1024, ten bits
+            // in bits [110, 120) of the piece (fb_pack below); the values travel as 22-bit floats, 13 mantissa bits rounded to nearest, so a hop
+            // adds at most 2^-14 of the running partial sum: after nkb hops at most nkb 2^-14 of the largest partial sum, about sqrt(nkb / 6)
+            // 2^-14 / sqrt(3) of it as a random walk (L = 32768: 171 hops, 1e-2 worst case, 5e-4 typical).  Where keys share a large component
+            // the partial sums exceed dQ (sum_j dS_ij = 0) by the same factor as the bf16 rounding of dS is amplified, and that rounding stays
+            // the larger term: tests/test_attention_paths.py holds the chained dq to the two-kernel pair's at L = 32768.  Unpacked form
+            // (FB_PACK 0): c mod 4096, three bits in the lowest mantissa bits of each of the four dwords (2^-20 relative per hop).
+            // A piece is accepted only with exactly that number: the
             // consumer polls a line that is being rewritten, and what comes back is not always the newest version (measured: under a burst of L2
             // evictions a poll can return the line as it was two or four writes ago, whole 128-byte lines at a time) — every piece has to prove
             // which write it belongs to.  (Three values + a 32-bit number per piece was built too: exact values, a third of the vector-ALU work,

@@ -63,4 +63,30 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def block_errors(a, b, rows=64, floor=1e-3, scale=None, floor_max=1e-5):
+    """Relative L2 error per block of `rows` rows, and over everything.  a, b: (..., L, C) — e.g. (batch, head, L, head_dim); the last
+    block of each leading index may be ragged.  A block's denominator is at least `floor` x the median block norm of b and `floor_max` x
+    the largest, so blocks whose reference cancels to about zero (or carries no weight at all) do not dominate.  `scale` (same shape as b):
+    measure against its norms instead of b's — the magnitude a sum's rounding is relative to when its terms cancel.
+    Returns (per-block errors of shape (..., blocks), global error)."""
+    a, b = a.detach().double(), b.detach().double()
+    L = a.shape[-2]
+    nb = (L + rows - 1) // rows
+    pad = nb * rows - L
+    d = torch.nn.functional.pad((a - b).pow(2).sum(-1), (0, pad))
+    r = torch.nn.functional.pad((b if scale is None else scale.double()).pow(2).sum(-1), (0, pad))
+    err = d.reshape(*d.shape[:-1], nb, rows).sum(-1).sqrt()
+    ref = r.reshape(*r.shape[:-1], nb, rows).sum(-1).sqrt()
+    den = ref.clamp_min(max(floor * float(ref.flatten().median()), floor_max * float(ref.max())) + 1e-300)
+    return err / den, float(d.sum().sqrt() / (r.sum().sqrt() + 1e-300))
+
+
+def block_rel_l2(a, b, rows=64, floor=1e-3, scale=None, floor_max=1e-5):
+    """block_errors reduced: (max block error, global error, index of the worst block).  NaN anywhere counts as the worst."""
+    blk, glob = block_errors(a, b, rows, floor, scale, floor_max)
+    flat = blk.flatten()
+    worst = int(torch.nan_to_num(flat, nan=float("inf")).argmax())
+    return float(flat[worst]), glob, tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), blk.shape))
+
+
 TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2}
