@@ -159,6 +159,11 @@ int od_qk_norm_rope_bwd(int dtype, const void* qkv, int ldqkv, const float* wq, 
  * replaces: attn.py:82 (F.scaled_dot_product_attention). */
 int od_flash_attn_fwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                       float* lse, int B, int H, int L, int hd, float scale, int q_prescaled, void* stream);
+/* Varlen form: sequence b of the padded (B, L) layout is valid for rows < lens[b] (device int32 [B], 1 <= lens[b] <= L; L stays the
+ * row stride).  Keys >= lens[b] are never read; query rows >= lens[b] of o and lse are written as 0.  Same (dtype, hd) set and the
+ * same kernel choice (by the padded L) as od_flash_attn_fwd.  replaces: attn.py:82 on sequences zero-padded to a common length. */
+int od_flash_attn_fwd_varlen(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                             float* lse, const int* lens, int B, int H, int L, int hd, float scale, int q_prescaled, void* stream);
 /* dq,dk,dv from do; delta fp32 [B][H][L] is workspace. */
 int od_flash_attn_bwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
                       int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk,
@@ -202,6 +207,10 @@ int od_flash_attn_bwd_passes(void);
 /* y[b][l][c] = bias[c] + sum_j w[c][j] x[b][l+j-r][c], zero padded; ksize in {3, 5, 7, 9}.  replaces: swiglu.py:20, model.py:59,62. */
 int od_dwconv(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, int B, int L,
               int C, int ksize, void* stream);
+/* the same per sequence of valid length lens[b] (device int32 [B]): taps at frames >= lens[b] read as zero, outputs there are
+ * written as zero.  replaces: swiglu.py:20, model.py:59,62 on sequences zero-padded to a common length. */
+int od_dwconv_varlen(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, const int* lens,
+                     int B, int L, int C, int ksize, void* stream);
 int od_dwconv_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx,
                   float* dw, float* db, int B, int L, int C, int ksize, void* stream);
 /* x[(b,l)][c] *= scale[b][c] in place (scale fp32 [B][C]): nn.Dropout1d in training mode — the host draws 0 or 1/(1-p) per
@@ -225,6 +234,10 @@ int od_final_norm_proj_out_bwd(int dtype, const void* x, int ldx, const float* i
 int od_uhead_fwd(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
                  const float* b3, const float* w4, const float* b4, float* fsum, int B, int E, int L, int U,
                  void* stream);
+/* the same over frames < lens[b] (device int32 [B]); both k = 3 convs zero-pad at lens[b].  replaces: model.py:58-65,99 per sequence. */
+int od_uhead_fwd_varlen(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
+                        const float* b3, const float* w4, const float* b4, float* fsum, const int* lens, int B, int E, int L,
+                        int U, void* stream);
 /* parameter gradients of the stack given dfm[b][c] = dLoss/d(mean_l act2[b][c]). */
 int od_uhead_bwd(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
                  const float* b3, const float* w4, const float* b4, const float* dfm, float* dw0, float* db0, float* dw1,
@@ -232,6 +245,9 @@ int od_uhead_bwd(const float* xt, const float* w0, const float* b0, const float*
 /* u[b] = u_scale*softplus(w_out . (f*(1+mod[0:U]) + mod[U:2U]) + b_out), f = fsum/L.  replaces: model.py:100-102. */
 int od_uhead_tail(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, int B, int U,
                   int L, float u_scale, void* stream);
+/* the same with f = fsum/lens[b] (device int32 [B]).  replaces: model.py:99-102 (the mean over a sequence's own frames). */
+int od_uhead_tail_varlen(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, const int* lens,
+                         int B, int U, int L, float u_scale, void* stream);
 /* backward of the tail: dfm[b][c], dmod[b][2U], dw_out[U] +=, db_out[1] += from du[b]. */
 int od_uhead_tail_bwd(const float* fsum, const float* mod, const float* w_out, const float* b_out, const float* du,
                       float* dfm, float* dmod, float* dw_out, float* db_out, int B, int U, int L, float u_scale,
@@ -250,6 +266,13 @@ int od_loss_finalize(const float* sums, const float* dsq, const float* u, float*
 int od_sampler_step(float* x, const float* u, const float* v, const float* eta, int B, int E, int L, void* stream);
 /* eta[0] = 1 - (sqrt(c0)/max(mean(u), sqrt(c0)+1e-6))^(1/num_steps); also eta[1] = mean(u).  replaces: model.py:131-132. */
 int od_sampler_eta(const float* u, float* eta, int B, float c0, int num_steps, void* stream);
+/* per song g of G (rows [offs[g], offs[g+1]), offs device int32 [G+1]): eta[g][0..1] as od_sampler_eta computes them over those rows
+ * alone, bit for bit (same summation order).  replaces: model.py:131-132, once per song of a batch. */
+int od_sampler_eta_groups(const float* u, const int* offs, float* eta, int G, float c0, int num_steps, void* stream);
+/* x[b] -= eta[g(b)][0] * u[b] * v[b] over frames < lens[b]; frames >= lens[b] of x are written as 0 (g(b): the song holding row b).
+ * replaces: model.py:136, per song of a batch. */
+int od_sampler_step_varlen(float* x, const float* u, const float* v, const float* eta, const int* lens, const int* offs, int G,
+                           int B, int E, int L, void* stream);
 
 /* ---- deterministic accumulation (OD_DETERMINISTIC=1 in the Python host; not part of the reference's path) ------------------
  * The step forms its weight / bias / modulation gradients and its loss scalars with fp32 atomics, whose order — and therefore last bits —

@@ -103,16 +103,31 @@ __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d
 }
 __device__ __forceinline__ void st4(f32x3_t* p, float a, float b, float c, float d) { st4((float*)p, a, b, c, d); }
 
+// varlen (VL) forms of the forward kernels: lens[b] is sequence b's valid length Lb (1 <= Lb <= L) in the padded (B, L) layout.
+// A query tile that starts at or past Lb writes zeros (o rows and lse) over its rows < L and skips the key loop.
+template <int HD, int ES>
+__device__ __forceinline__ void attn_zero_rows(void* o, int ldo, float* lse, int b, int h, int H, int L, int r0, int nrows) {
+    constexpr int CPR = HD * ES / 16;                     // 16-byte chunks per row of a head
+    const int r1 = r0 + nrows < L ? r0 + nrows : L;
+    unsigned char* ob = (unsigned char*)o + (size_t)h * HD * ES;
+    for (int i = threadIdx.x; i < (r1 - r0) * CPR; i += blockDim.x) {
+        const int row = r0 + i / CPR, ch = i % CPR;
+        *(u32x4*)(ob + ((size_t)b * L + row) * ldo * ES + ch * 16) = (u32x4)(0u);
+    }
+    for (int row = r0 + (int)threadIdx.x; row < r1; row += blockDim.x) lse[((size_t)b * H + h) * L + row] = 0.f;
+}
+
 // ======================================================================== forward
 // block: 4 waves x NQT 16-query tiles (32 or 16 query rows per wave); loop over 64-key tiles, double-buffered in LDS.
 // NQT = 1 halves a wave's work and its registers: at sampler sizes (B*H*L/32 = 2240 waves of work against 2048 wave slots at two waves per
 // SIMD) the 32-query form runs two rounds for 1.09 rounds of work.
 // PRE: q arrives multiplied by scale*log2(e) (od_qk_norm_rope's q_scale), so q.k is already the base-2 exponent and
 // the per-element multiply disappears from the loop.
-template <class T, int HD, int NW, bool PRE, int NQT = 2>
+template <class T, int HD, int NW, bool PRE, int NQT = 2, bool VL = false>
 __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_fwd_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                            const T* __restrict__ v, int ldv, T* __restrict__ o, int ldo,
-                                                           float* __restrict__ lse, int B, int H, int L, float scale) {
+                                                           float* __restrict__ lse, int B, int H, int L, float scale,
+                                                           const int* __restrict__ lens = nullptr) {
     using St = Stage<T, HD>;
     constexpr int NS = HD / 32;   // 32-deep slabs over the head dim
     constexpr int ND = HD / 16;   // 16-row tiles over the head dim
@@ -122,6 +137,8 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
     int qt, bh;
     if (!attn_block_coords(nqt, B * H, qt, bh)) return;
     const int b = bh / H, h = bh % H;
+    const int Lb = VL ? od_uniform(lens[b]) : L;        // valid length (L stays the row stride)
+    if (VL && qt * QB >= Lb) { attn_zero_rows<HD, sizeof(T)>(o, ldo, lse, b, h, H, L, qt * QB, QB); return; }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, x = lane & 15, g = lane >> 4;
     const T* qb = q + (size_t)b * L * ldq + h * HD;
     const T* kb = k + (size_t)b * L * ldk + h * HD;
@@ -132,7 +149,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
     od_frag<T> fq[NQT][NS];
 #pragma unroll
     for (int qi = 0; qi < NQT; qi++) {
-        int row = q0 + qi * 16 + x; row = row < L ? row : L - 1;
+        int row = q0 + qi * 16 + x; row = row < Lb ? row : Lb - 1;
 #pragma unroll
         for (int s = 0; s < NS; s++) od_frag_load(fq[qi][s], qb + (size_t)row * ldq + s * 32 + g * 8);
     }
@@ -156,7 +173,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
 #endif
     const float inv_c = 1.0f / c;
 
-    const int nkt = (L + 63) / 64;
+    const int nkt = (Lb + 63) / 64;
     St sk, sv;
     auto lstore = [&](unsigned char* base) {
         sk.store_rowmajor(base);
@@ -164,11 +181,11 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
     };
     // bf16: K/V tiles go global -> LDS by LDS-DMA; f32 (V must be transposed) stages through registers
     auto dma = [&](int kt, unsigned char* base) {
-        St::template dma_rowmajor<NW>(kb, ldk, kt * 64, L, base);
-        St::template dma_rowmajor<NW>(vb, ldv, kt * 64, L, base + St::BYTES);
+        St::template dma_rowmajor<NW>(kb, ldk, kt * 64, Lb, base);
+        St::template dma_rowmajor<NW>(vb, ldv, kt * 64, Lb, base + St::BYTES);
     };
     if constexpr (St::TR) dma(0, smem);
-    else { sk.load(kb, ldk, 0, L); sv.load(vb, ldv, 0, L); lstore(smem); }
+    else { sk.load(kb, ldk, 0, Lb); sv.load(vb, ldv, 0, Lb); lstore(smem); }
     __syncthreads();
     auto tile = [&](int kt, auto masked_t, auto first_t) {
         constexpr bool MASKED = decltype(masked_t)::value;
@@ -177,7 +194,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
         const unsigned char* tV = tK + St::BYTES;
         if (kt + 1 < nkt) {
             if constexpr (St::TR) dma(kt + 1, smem + ((kt + 1) & 1) * 2 * St::BYTES);
-            else { sk.load(kb, ldk, (kt + 1) * 64, L); sv.load(vb, ldv, (kt + 1) * 64, L); }
+            else { sk.load(kb, ldk, (kt + 1) * 64, Lb); sv.load(vb, ldv, (kt + 1) * 64, Lb); }
         }
 
         // S^T tiles: rows = keys (4 tiles of 16), cols = queries; accumulators start at -mref
@@ -196,14 +213,14 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
             }
         }
         const int kbase = kt * 64;
-        if constexpr (MASKED) {    // ragged last tile only: mask keys >= L
+        if constexpr (MASKED) {    // ragged last tile only: mask keys >= L (VL: >= Lb)
 #pragma unroll
             for (int qi = 0; qi < NQT; qi++)
 #pragma unroll
                 for (int t4 = 0; t4 < 4; t4++)
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (kbase + t4 * 16 + 4 * g + r >= L) e[qi][t4][r] = NEG_BIG;
+                        if (kbase + t4 * 16 + 4 * g + r >= Lb) e[qi][t4][r] = NEG_BIG;
         }
         // lane-local maxima (lane owns query column x, keys 16*t4 + 4g + r)
         float mx[NQT];
@@ -260,7 +277,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
         if constexpr (!St::TR) { if (kt + 1 < nkt) lstore(smem + ((kt + 1) & 1) * 2 * St::BYTES); }
         __syncthreads();
     };
-    const int nfull = L / 64;
+    const int nfull = Lb / 64;
     if (nfull > 0) tile(0, std::false_type{}, std::true_type{});
     else tile(0, std::true_type{}, std::true_type{});
     for (int kt = 1; kt < nfull; kt++) tile(kt, std::false_type{}, std::false_type{});
@@ -273,11 +290,13 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
         const float inv = 1.f / l;
         const int row = q0 + qi * 16 + x;
         if (row < L) {
+            const bool z = VL && row >= Lb;             // padded query rows: zeros, by selection
             T* orow = o + ((size_t)b * L + row) * ldo + h * HD;
 #pragma unroll
             for (int dt = 0; dt < ND; dt++)
-                st4(orow + dt * 16 + 4 * g, oacc[qi][dt][0] * inv, oacc[qi][dt][1] * inv, oacc[qi][dt][2] * inv, oacc[qi][dt][3] * inv);
-            if (g == 0) lse[((size_t)b * H + h) * L + row] = (mref[qi] * c + log2f(l)) * LN2;
+                st4(orow + dt * 16 + 4 * g, z ? 0.f : oacc[qi][dt][0] * inv, z ? 0.f : oacc[qi][dt][1] * inv, z ? 0.f : oacc[qi][dt][2] * inv,
+                    z ? 0.f : oacc[qi][dt][3] * inv);
+            if (g == 0) lse[((size_t)b * H + h) * L + row] = z ? 0.f : (mref[qi] * c + log2f(l)) * LN2;
         }
     }
 }
@@ -290,10 +309,11 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_
 // vector-ALU operations per wave and key tile beside 96 MFMAs: the kernel was bound by that (119 us per launch at the sampler's size, 0.51 PF/s
 // executed).  Now K fragments are 16-byte reads of the planes, V^T fragments transpose reads of the row-major planes (no transposed copy), the
 // probabilities are split as before (they are formed in registers), and the staging itself is the only split work left: a quarter of it.
-template <int NW, bool PRE, int NQT>
+template <int NW, bool PRE, int NQT, bool VL = false>
 __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
                                                                    const float* __restrict__ v, int ldv, float* __restrict__ o, int ldo,
-                                                                   float* __restrict__ lse, int B, int H, int L, float scale) {
+                                                                   float* __restrict__ lse, int B, int H, int L, float scale,
+                                                                   const int* __restrict__ lens = nullptr) {
     constexpr int HD = 64, PL = 64 * 128;          // one bf16 plane of a 64-row tile
     constexpr int STAGE = 4 * PL;                  // K hi, K lo, V hi, V lo
     static_assert(NW == 4, "the staging maps 1024 chunks of a tile onto 256 threads");
@@ -303,6 +323,8 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
     int qt, bh;
     if (!attn_block_coords(nqt, B * H, qt, bh)) return;
     const int b = bh / H, h = bh % H;
+    const int Lb = VL ? od_uniform(lens[b]) : L;        // valid length (L stays the row stride)
+    if (VL && qt * QB >= Lb) { attn_zero_rows<HD, 4>(o, ldo, lse, b, h, H, L, qt * QB, QB); return; }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, x = lane & 15, g = lane >> 4;
     const float* qb = q + (size_t)b * L * ldq + h * HD;
     const float* kb = k + (size_t)b * L * ldk + h * HD;
@@ -313,7 +335,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
     od_frag<f32x3_t> fq[NQT][2];
 #pragma unroll
     for (int qi = 0; qi < NQT; qi++) {
-        int row = q0 + qi * 16 + x; row = row < L ? row : L - 1;
+        int row = q0 + qi * 16 + x; row = row < Lb ? row : Lb - 1;
 #pragma unroll
         for (int s = 0; s < 2; s++) od_frag_load(fq[qi][s], (const f32x3_t*)(qb + (size_t)row * ldq + s * 32 + g * 8));
     }
@@ -326,14 +348,14 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
         for (int dt = 0; dt < 4; dt++) oacc[qi][dt] = (f32x4)(0.f);
     }
     const float inv_c = 1.0f / c;
-    const int nkt = (L + 63) / 64;
+    const int nkt = (Lb + 63) / 64;
     // staging: chunk cc = threadIdx.x + 256 i (i = 0..3) of the 64 x 16 fp32 chunks of a tile: row cc / 16, floats 4 (cc % 16) .. + 3
     u32x4 rk[4], rv[4];
     auto gload = [&](int kt) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int cc = threadIdx.x + 256 * i, row = cc >> 4, ch = cc & 15;
-            int gr = kt * 64 + row; gr = gr < L ? gr : L - 1;
+            int gr = kt * 64 + row; gr = gr < Lb ? gr : Lb - 1;
             rk[i] = *(const u32x4*)(kb + (size_t)gr * ldk + ch * 4);
             rv[i] = *(const u32x4*)(vb + (size_t)gr * ldv + ch * 4);
         }
@@ -386,7 +408,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
                 for (int t4 = 0; t4 < 4; t4++)
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (kbase + t4 * 16 + 4 * g + r >= L) e[qi][t4][r] = NEG_BIG;
+                        if (kbase + t4 * 16 + 4 * g + r >= Lb) e[qi][t4][r] = NEG_BIG;
         }
         float mx[NQT];
 #pragma unroll
@@ -444,7 +466,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
         if (kt + 1 < nkt) lstore(smem + ((kt + 1) & 1) * STAGE);
         __syncthreads();
     };
-    const int nfull = L / 64;
+    const int nfull = Lb / 64;
     if (nfull > 0) tile(0, std::false_type{}, std::true_type{});
     else tile(0, std::true_type{}, std::true_type{});
     for (int kt = 1; kt < nfull; kt++) tile(kt, std::false_type{}, std::false_type{});
@@ -457,11 +479,13 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_fwd_x3p_kernel(const float* 
         const float inv = 1.f / l;
         const int row = q0 + qi * 16 + x;
         if (row < L) {
+            const bool z = VL && row >= Lb;             // padded query rows: zeros, by selection
             float* orow = o + ((size_t)b * L + row) * ldo + h * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; dt++)
-                st4(orow + dt * 16 + 4 * g, oacc[qi][dt][0] * inv, oacc[qi][dt][1] * inv, oacc[qi][dt][2] * inv, oacc[qi][dt][3] * inv);
-            if (g == 0) lse[((size_t)b * H + h) * L + row] = (mref[qi] * c + log2f(l)) * LN2;
+                st4(orow + dt * 16 + 4 * g, z ? 0.f : oacc[qi][dt][0] * inv, z ? 0.f : oacc[qi][dt][1] * inv, z ? 0.f : oacc[qi][dt][2] * inv,
+                    z ? 0.f : oacc[qi][dt][3] * inv);
+            if (g == 0) lse[((size_t)b * H + h) * L + row] = z ? 0.f : (mref[qi] * c + log2f(l)) * LN2;
         }
     }
 }
@@ -499,10 +523,11 @@ template <> __device__ __forceinline__ f32x16_t od_mma32<f16_t>(s16x8 a, s16x8 b
 #ifndef OD_FWD32_OCC2
 #define OD_FWD32_OCC2 2     // waves per SIMD asked of the register allocator at 64 queries per wave
 #endif
-template <int NW, int NQB, bool PRE, class TA = bf16_t>
+template <int NW, int NQB, bool PRE, class TA = bf16_t, bool VL = false>
 __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash_fwd32_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ k, int ldk,
                                                                  const bf16_t* __restrict__ v, int ldv, bf16_t* __restrict__ o, int ldo,
-                                                                 float* __restrict__ lse, int B, int H, int L, float scale) {
+                                                                 float* __restrict__ lse, int B, int H, int L, float scale,
+                                                                 const int* __restrict__ lens = nullptr) {
     using St = Stage<bf16_t, 64>;
     constexpr int HD = 64, QB = NW * NQB * 32, STAGE = 2 * St::BYTES;
     static_assert(NW == 4 || NW == 8, "the K/V tiles are streamed as 2 + 2 (four waves) or 1 + 1 (eight waves) one-KiB pieces per wave");
@@ -511,15 +536,17 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
     int qt, bh;
     if (!attn_block_coords(nqt, B * H, qt, bh)) return;
     const int b = bh / H, h = bh % H;
+    const int Lb = VL ? od_uniform(lens[b]) : L;        // valid length (L stays the row stride)
+    if (VL && qt * QB >= Lb) { attn_zero_rows<HD, 2>(o, ldo, lse, b, h, H, L, qt * QB, QB); return; }
     const int lane = threadIdx.x & 63, wave = od_uniform(threadIdx.x >> 6), c32 = lane & 31, hi = lane >> 5, x = lane & 15, g4 = lane >> 4;
     const bf16_t* qb_ = q + (size_t)b * L * ldq + h * HD;
     const int q0 = qt * QB + wave * NQB * 32;
     const float c = PRE ? 1.f : scale * LOG2E, inv_c = 1.0f / c;
 
     // K / V tiles by buffer-addressed LDS-DMA: per-lane offset fixed for the whole kernel, one scalar add per tile;
-    // rows >= L lie past the end of the descriptor and read as zero
-    const od_srd_t rk = od_make_srd(k + (size_t)b * L * ldk + h * HD, (unsigned)(((size_t)(L - 1) * ldk + HD) * 2));
-    const od_srd_t rv = od_make_srd(v + (size_t)b * L * ldv + h * HD, (unsigned)(((size_t)(L - 1) * ldv + HD) * 2));
+    // rows >= L (VL: >= Lb) lie past the end of the descriptor and read as zero
+    const od_srd_t rk = od_make_srd(k + (size_t)b * L * ldk + h * HD, (unsigned)(((size_t)(Lb - 1) * ldk + HD) * 2));
+    const od_srd_t rv = od_make_srd(v + (size_t)b * L * ldv + h * HD, (unsigned)(((size_t)(Lb - 1) * ldv + HD) * 2));
     // piece = 8 rows x 128 B; the swizzle (swz32, od_tiles.h) is applied on the SOURCE column; a wave's two pieces (w, w + 4)
     // have the same row bits 3..0, so one per-lane offset serves both
     // (eight waves: wave w moves piece w of each tile alone; the per-lane offsets are the same expression with the piece index w)
@@ -537,7 +564,7 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
     s16x8 fq[NQB][4];
 #pragma unroll
     for (int qi = 0; qi < NQB; qi++) {
-        int row = q0 + qi * 32 + c32; row = row < L ? row : L - 1;
+        int row = q0 + qi * 32 + c32; row = row < Lb ? row : Lb - 1;
 #pragma unroll
         for (int s4 = 0; s4 < 4; s4++) fq[qi][s4] = *(const s16x8*)(qb_ + (size_t)row * ldq + s4 * 16 + hi * 8);
     }
@@ -549,7 +576,7 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
         minit[qi] = (f32x16_t)(0.f);
         oacc[qi][0] = (f32x16_t)(0.f); oacc[qi][1] = (f32x16_t)(0.f);
     }
-    const int nkt = (L + 63) / 64;
+    const int nkt = (Lb + 63) / 64;
     // lane-constant LDS byte offsets inside a stage: K fragment (key row c32 (+32), 16-byte slot 2 s + hi) and V transpose-read
     // chunk (rows 4 (g4 >> 1) + (x >> 2) (+8, +16, ...) of the tile, feature column 16 (g4 & 1) + 4 (x & 3) (+32))
     int offK[4], offV[2][2];
@@ -594,7 +621,7 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
                 if constexpr (MASKED) {    // ragged last tile only: keys >= L
 #pragma unroll
                     for (int r = 0; r < 16; r++)
-                        if (kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= L) sa[kb][r] = NEG_BIG;
+                        if (kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= Lb) sa[kb][r] = NEG_BIG;
                 }
             }
             // exact path: move the reference to the row maximum (always on the first tile; otherwise only when the guard trips)
@@ -662,7 +689,7 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
     // the two LDS stages alternate with compile-time addresses: the loop body is unrolled by two
     unsigned char* const s0 = smem;
     unsigned char* const s1 = smem + STAGE;
-    const int nfull = L / 64;
+    const int nfull = Lb / 64;
     if (nfull > 0) tile(0, s0, s1, std::false_type{}, std::true_type{});
     else tile(0, s0, s1, std::true_type{}, std::true_type{});
     int kt = 1;
@@ -679,14 +706,15 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
         const float inv = 1.f / l;
         const int row = q0 + qi * 32 + c32;
         if (row < L) {
+            const bool z = VL && row >= Lb;             // padded query rows: zeros, by selection
             bf16_t* orow = o + ((size_t)b * L + row) * ldo + h * HD;
 #pragma unroll
             for (int db = 0; db < 2; db++)
 #pragma unroll
                 for (int t4 = 0; t4 < 4; t4++)
-                    st4(orow + db * 32 + 8 * t4 + 4 * hi, oacc[qi][db][4 * t4] * inv, oacc[qi][db][4 * t4 + 1] * inv,
-                        oacc[qi][db][4 * t4 + 2] * inv, oacc[qi][db][4 * t4 + 3] * inv);
-            if (hi == 0) lse[((size_t)b * H + h) * L + row] = (mref[qi] + log2f(l)) * LN2;
+                    st4(orow + db * 32 + 8 * t4 + 4 * hi, z ? 0.f : oacc[qi][db][4 * t4] * inv, z ? 0.f : oacc[qi][db][4 * t4 + 1] * inv,
+                        z ? 0.f : oacc[qi][db][4 * t4 + 2] * inv, z ? 0.f : oacc[qi][db][4 * t4 + 3] * inv);
+            if (hi == 0) lse[((size_t)b * H + h) * L + row] = z ? 0.f : (mref[qi] + log2f(l)) * LN2;
         }
     }
 }
@@ -713,10 +741,11 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
 // one box, 311.6 against 314.6 ms per step (profiles/r06g_ab_fwd16x.txt) — the 16x16x32 MFMA draws ~7 % less per FLOP on a board whose power cap
 // sets the clock (profiles/r03u_mfma_power.txt), which the issue model of round 2 (twice the MFMA issue slots: -12 %) did not know about.
 // bf16 or IEEE-half operands (TA), head_dim 64, q pre-multiplied by scale * log2(e).
-template <int NW, int NQT, class TA>
+template <int NW, int NQT, class TA, bool VL = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ k, int ldk,
                                                                   const bf16_t* __restrict__ v, int ldv, bf16_t* __restrict__ o, int ldo,
-                                                                  float* __restrict__ lse, int B, int H, int L) {
+                                                                  float* __restrict__ lse, int B, int H, int L,
+                                                                  const int* __restrict__ lens = nullptr) {
     using T = TA;                                   // the MFMA operand type: q, k, v hold bf16 or IEEE half (same 16-bit containers); o is bf16
     using St = Stage<bf16_t, 64>;
     constexpr int HD = 64, QB = NW * 16 * NQT, STAGE = 2 * St::BYTES;
@@ -726,11 +755,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
     int qt, bh;
     if (!attn_block_coords(nqt, B * H, qt, bh)) return;
     const int b = bh / H, h = bh % H;
+    const int Lb = VL ? od_uniform(lens[b]) : L;        // valid length (L stays the row stride)
+    if (VL && qt * QB >= Lb) { attn_zero_rows<HD, 2>(o, ldo, lse, b, h, H, L, qt * QB, QB); return; }
     const int lane = threadIdx.x & 63, wave = od_uniform(threadIdx.x >> 6), x = lane & 15, g = lane >> 4;
     const bf16_t* qb = q + (size_t)b * L * ldq + h * HD;
     const int q0 = qt * QB + wave * 16 * NQT;
-    const od_srd_t rk = od_make_srd(k + (size_t)b * L * ldk + h * HD, (unsigned)(((size_t)(L - 1) * ldk + HD) * 2));
-    const od_srd_t rv = od_make_srd(v + (size_t)b * L * ldv + h * HD, (unsigned)(((size_t)(L - 1) * ldv + HD) * 2));
+    const od_srd_t rk = od_make_srd(k + (size_t)b * L * ldk + h * HD, (unsigned)(((size_t)(Lb - 1) * ldk + HD) * 2));
+    const od_srd_t rv = od_make_srd(v + (size_t)b * L * ldv + h * HD, (unsigned)(((size_t)(Lb - 1) * ldv + HD) * 2));
     // piece = 8 rows x 128 B, tile_off<128>'s swizzle (slot ^ (row & 7), row & 7 = lane >> 3) applied on the SOURCE column; a wave moves pieces w, w + 4
     const int prow = lane >> 3, pslot = (lane & 7) ^ prow;
     const unsigned vk = (unsigned)((wave * 8 + prow) * ldk * 2 + pslot * 16), vv = (unsigned)((wave * 8 + prow) * ldv * 2 + pslot * 16);
@@ -744,7 +775,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
     od_frag<T> fq[NQT][2];
 #pragma unroll
     for (int qi = 0; qi < NQT; qi++) {
-        int row = q0 + qi * 16 + x; row = row < L ? row : L - 1;
+        int row = q0 + qi * 16 + x; row = row < Lb ? row : Lb - 1;
 #pragma unroll
         for (int s2 = 0; s2 < 2; s2++) od_frag_load(fq[qi][s2], (const TA*)(qb + (size_t)row * ldq + s2 * 32 + g * 8));
     }
@@ -756,7 +787,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
 #pragma unroll
         for (int dt = 0; dt < 4; dt++) oacc[qi][dt] = (f32x4)(0.f);
     }
-    const int nkt = (L + 63) / 64;
+    const int nkt = (Lb + 63) / 64;
     OD_DRAIN_VMEM();                                // the Q fragments: a wait hipcc sees (see flash_fwd32_kernel)
     dma(0, smem);
     OD_WAIT_VMCNT(0);
@@ -789,7 +820,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
                 for (int t4 = 0; t4 < 4; t4++)
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (kt * 64 + t4 * 16 + 4 * g + r >= L) e[qi][t4][r] = NEG_BIG;
+                        if (kt * 64 + t4 * 16 + 4 * g + r >= Lb) e[qi][t4][r] = NEG_BIG;
         }
         od_frag<T> fp[NQT][2];
 #pragma unroll
@@ -846,7 +877,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
     };
     unsigned char* const s0 = smem;
     unsigned char* const s1 = smem + STAGE;
-    const int nfull = L / 64;
+    const int nfull = Lb / 64;
     if (nfull > 0) tile(0, s0, s1, std::false_type{}, std::true_type{});
     else tile(0, s0, s1, std::true_type{}, std::true_type{});
     int kt = 1;
@@ -864,11 +895,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
         const float inv = 1.f / l;
         const int row = q0 + qi * 16 + x;
         if (row < L) {
+            const bool z = VL && row >= Lb;             // padded query rows: zeros, by selection
             bf16_t* orow = o + ((size_t)b * L + row) * ldo + h * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; dt++)
-                st4(orow + dt * 16 + 4 * g, oacc[qi][dt][0] * inv, oacc[qi][dt][1] * inv, oacc[qi][dt][2] * inv, oacc[qi][dt][3] * inv);
-            if (g == 0) lse[((size_t)b * H + h) * L + row] = (mref[qi] + log2f(l)) * LN2;
+                st4(orow + dt * 16 + 4 * g, z ? 0.f : oacc[qi][dt][0] * inv, z ? 0.f : oacc[qi][dt][1] * inv, z ? 0.f : oacc[qi][dt][2] * inv,
+                    z ? 0.f : oacc[qi][dt][3] * inv);
+            if (g == 0) lse[((size_t)b * H + h) * L + row] = z ? 0.f : (mref[qi] + log2f(l)) * LN2;
         }
     }
 }
@@ -1240,9 +1273,10 @@ struct AttnAux {
 #endif
 };
 
-template <class T, int HD, bool PRE>
+// VL: the varlen forms (lens = device int32 [B] valid lengths); the kernel the dispatch picks depends on the padded L alone
+template <class T, int HD, bool PRE, bool VL = false>
 int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, float* lse, int B,
-               int H, int L, float scale, hipStream_t st) {
+               int H, int L, float scale, hipStream_t st, const int* lens = nullptr) {
     if constexpr (std::is_same<T, f16_t>::value) {          // half operands: q, k, v are IEEE half, o is written as bf16 (head_dim 64 only)
         static_assert(HD == 64, "the half-operand forward exists for head_dim 64");
 #if OD_FWD16X
@@ -1250,16 +1284,16 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
         if (PRE && L >= fwd16x_min_l_h) {
             constexpr int NQT = OD_FWD16X_NQT;
             const int grid = attn_grid((L + 4 * 16 * NQT - 1) / (4 * 16 * NQT), B * H);
-            OD_LAUNCH_DYN((flash_fwd16x_kernel<4, NQT, f16_t>), dim3(grid), dim3(256), (4 * Stage<bf16_t, HD>::BYTES), st, (const bf16_t*)q, ldq,
-                          (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L);
+            OD_LAUNCH_DYN((flash_fwd16x_kernel<4, NQT, f16_t, VL>), dim3(grid), dim3(256), (4 * Stage<bf16_t, HD>::BYTES), st, (const bf16_t*)q, ldq,
+                          (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, lens);
             OD_CHECK_LAUNCH();
             return 0;
         }
 #endif
         constexpr int NW = 4, NQB = OD_FWD32_NQB;
         const int grid = attn_grid((L + NW * NQB * 32 - 1) / (NW * NQB * 32), B * H);
-        OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE, f16_t>), dim3(grid), dim3(64 * NW), (4 * Stage<bf16_t, HD>::BYTES), st, (const bf16_t*)q, ldq,
-                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, scale);
+        OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE, f16_t, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<bf16_t, HD>::BYTES), st, (const bf16_t*)q, ldq,
+                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
     } else {
@@ -1274,8 +1308,8 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
       if constexpr (std::is_same<T, bf16_t>::value && HD == 64 && PRE) {
         constexpr int NQT = OD_FWD16X_NQT, NWX = OD_FWD16X_NW;
         const int grid = attn_grid((L + NWX * 16 * NQT - 1) / (NWX * 16 * NQT), B * H);
-        OD_LAUNCH_DYN((flash_fwd16x_kernel<NWX, NQT, bf16_t>), dim3(grid), dim3(64 * NWX), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
-                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L);
+        OD_LAUNCH_DYN((flash_fwd16x_kernel<NWX, NQT, bf16_t, VL>), dim3(grid), dim3(64 * NWX), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
+                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, lens);
         OD_CHECK_LAUNCH();
         return 0;
       }
@@ -1284,8 +1318,8 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
     if constexpr (OD_FWD32 && std::is_same<T, bf16_t>::value && HD == 64) {
         constexpr int NW = OD_FWD32_NW, NQB = OD_FWD32_NQB;
         const int grid = attn_grid((L + NW * NQB * 32 - 1) / (NW * NQB * 32), B * H);
-        OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
-                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, scale);
+        OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE, bf16_t, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
+                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
     }
@@ -1297,8 +1331,8 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
 #endif
     if constexpr (OD_FWD_X3P && std::is_same<T, f32x3_t>::value && HD == 64) {
         const int grid = attn_grid((L + 4 * 16 * OD_X3P_NQT - 1) / (4 * 16 * OD_X3P_NQT), B * H);
-        OD_LAUNCH_DYN((flash_fwd_x3p_kernel<4, PRE, OD_X3P_NQT>), dim3(grid), dim3(256), (2 * 4 * 64 * 128), st, (const float*)q, ldq, (const float*)k, ldk,
-                      (const float*)v, ldv, (float*)o, ldo, lse, B, H, L, scale);
+        OD_LAUNCH_DYN((flash_fwd_x3p_kernel<4, PRE, OD_X3P_NQT, VL>), dim3(grid), dim3(256), (2 * 4 * 64 * 128), st, (const float*)q, ldq, (const float*)k, ldk,
+                      (const float*)v, ldv, (float*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
     }
@@ -1308,14 +1342,14 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
     const int blocks2 = ((L + NW * 32 - 1) / (NW * 32)) * B * H;
     if (std::is_same<T, float>::value && HD == 64 && blocks2 < nqt1_below) {
         const int grid = attn_grid((L + NW * 16 - 1) / (NW * 16), B * H);
-        OD_LAUNCH_DYN((flash_fwd_kernel<T, HD, NW, PRE, 1>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv,
-                  (T*)o, ldo, lse, B, H, L, scale);
+        OD_LAUNCH_DYN((flash_fwd_kernel<T, HD, NW, PRE, 1, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv,
+                  (T*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
     }
     const int grid = attn_grid((L + NW * 32 - 1) / (NW * 32), B * H);
-    OD_LAUNCH_DYN((flash_fwd_kernel<T, HD, NW, PRE>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv,
-              (T*)o, ldo, lse, B, H, L, scale);
+    OD_LAUNCH_DYN((flash_fwd_kernel<T, HD, NW, PRE, 2, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv,
+              (T*)o, ldo, lse, B, H, L, scale, lens);
     OD_CHECK_LAUNCH();
     return 0;
     }
@@ -1364,6 +1398,25 @@ extern "C" int od_flash_attn_fwd(int dtype, const void* q, int ldq, const void* 
     hipStream_t st = (hipStream_t)stream;
 #define FWD(TT, HDV) (q_prescaled ? launch_fwd<TT, HDV, true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, L, scale, st) \
                                   : launch_fwd<TT, HDV, false>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, L, scale, st))
+    if (dtype == OD_BF16 && hd == 64) return FWD(bf16_t, 64);
+    if (dtype == OD_F16 && hd == 64) return FWD(f16_t, 64);
+    if (dtype == OD_BF16 && hd == 32) return FWD(bf16_t, 32);
+    if (dtype == OD_F32 && hd == 64) return FWD(float, 64);
+    if (dtype == OD_F32 && hd == 32) return FWD(float, 32);
+    if (dtype == OD_F32X3 && hd == 64) return FWD(f32x3_t, 64);
+    if (dtype == OD_F32X3 && hd == 32) return FWD(f32x3_t, 32);
+#undef FWD
+    return OD_ERR_UNSUPPORTED;
+}
+
+extern "C" int od_flash_attn_fwd_varlen(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o,
+                                        int ldo, float* lse, const int* lens, int B, int H, int L, int hd, float scale, int q_prescaled,
+                                        void* stream) {
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return OD_ERR_ALIGN;
+    if (!lens) return OD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+#define FWD(TT, HDV) (q_prescaled ? launch_fwd<TT, HDV, true, true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, L, scale, st, lens) \
+                                  : launch_fwd<TT, HDV, false, true>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, L, scale, st, lens))
     if (dtype == OD_BF16 && hd == 64) return FWD(bf16_t, 64);
     if (dtype == OD_F16 && hd == 64) return FWD(f16_t, 64);
     if (dtype == OD_BF16 && hd == 32) return FWD(bf16_t, 32);

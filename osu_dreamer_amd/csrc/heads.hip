@@ -32,14 +32,15 @@ struct UHeadSmem {
     float w4s[MAXU][MAXU + 1];
 };
 
-// forward pass of one window into LDS; returns nothing.  l0 = first owned frame.
+// forward pass of one window into LDS; returns nothing.  l0 = first owned frame.  Lv = the sequence's valid length (frames >= Lv are
+// the zero padding of both k = 3 convs; L, the row stride, unless varlen)
 __device__ __forceinline__ void uhead_window_fwd(UHeadSmem& S, const float* __restrict__ xt, const UHeadW& P, int b, int l0,
-                                                 int E, int L, int U) {
+                                                 int E, int L, int U, int Lv) {
     const int t = threadIdx.x;
     for (int idx = t; idx < E * (UW + 4); idx += 256) {
         const int e = idx / (UW + 4), ix = idx % (UW + 4);
         const int f = l0 - 3 + ix;
-        S.xts[e][ix] = (f >= 0 && f < L) ? xt[((size_t)b * E + e) * L + f] : 0.f;
+        S.xts[e][ix] = (f >= 0 && f < Lv) ? xt[((size_t)b * E + e) * L + f] : 0.f;
     }
     __syncthreads();
     for (int idx = t; idx < E * (UW + 2); idx += 256) {
@@ -53,7 +54,7 @@ __device__ __forceinline__ void uhead_window_fwd(UHeadSmem& S, const float* __re
         float z = P.b1[c];
         for (int e = 0; e < E; e++) z += P.w1[c * E + e] * S.z0s[e][i2];
         S.z1s[c][i2] = z;
-        S.a1s[c][i2] = (f >= 0 && f < L) ? od_silu(z) : 0.f;
+        S.a1s[c][i2] = (f >= 0 && f < Lv) ? od_silu(z) : 0.f;
     }
     __syncthreads();
     for (int idx = t; idx < U * UW; idx += 256) {
@@ -68,10 +69,14 @@ __device__ __forceinline__ void uhead_load_w4(UHeadSmem& S, const UHeadW& P, int
     __syncthreads();
 }
 
+// VL: sequence b is valid for frames < Lb = lens[b]; windows whose owned frames all lie at or past Lb add nothing and are skipped
+template <bool VL = false>
 __global__ __launch_bounds__(256) void uhead_fwd_kernel(const float* __restrict__ xt, UHeadW P, float* __restrict__ fsum,
-                                                        int E, int L, int U, int nwin, int wpb, const OdDetTable* __restrict__ det) {
+                                                        int E, int L, int U, int nwin, int wpb, const OdDetTable* __restrict__ det,
+                                                        const int* __restrict__ lens = nullptr) {
     __shared__ UHeadSmem S;
     const int b = blockIdx.y, t = threadIdx.x;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     const int i = t & 31, grp = t >> 5, cpg = U / 8;
     uhead_load_w4(S, P, U);
     float acc[MAXU / 8];
@@ -81,9 +86,10 @@ __global__ __launch_bounds__(256) void uhead_fwd_kernel(const float* __restrict_
         const int win = blockIdx.x * wpb + wi;
         if (win >= nwin) break;
         const int l0 = win * UOWN;
-        uhead_window_fwd(S, xt, P, b, l0, E, L, U);
+        if (VL && l0 >= Lb) break;                    // block-uniform
+        uhead_window_fwd(S, xt, P, b, l0, E, L, U, Lb);
         const int f = l0 - 1 + i;
-        const bool own = (i >= 1 && i < UW - 1 && f < L);
+        const bool own = (i >= 1 && i < UW - 1 && f < Lb);
 #pragma unroll
         for (int q = 0; q < MAXU / 8; q++) {
             if (q < cpg) {
@@ -130,7 +136,7 @@ __global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict_
         const int win = blockIdx.x * UWPB + wi;
         if (win >= nwin) break;
         const int l0 = win * UOWN;
-        uhead_window_fwd(S, xt, P, b, l0, E, L, U);
+        uhead_window_fwd(S, xt, P, b, l0, E, L, U, L);
         const int f = l0 - 1 + i;
         const bool inr = (f >= 0 && f < L);
         const bool own = (i >= 1 && i < UW - 1 && f < L);
@@ -244,13 +250,16 @@ __global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict_
     }
 }
 
-// tail: f = fsum/L; fm = f*(1+mod[0:U]) + mod[U:2U]; y = w.fm + b; u = u_scale*softplus(y)
+// tail: f = fsum/L; fm = f*(1+mod[0:U]) + mod[U:2U]; y = w.fm + b; u = u_scale*softplus(y).  VL: f = fsum/lens[b]
+template <bool VL = false>
 __global__ void uhead_tail_kernel(const float* __restrict__ fsum, const float* __restrict__ mod, const float* __restrict__ w,
-                                  const float* __restrict__ bo, float* __restrict__ u, int B, int U, int L, float u_scale) {
+                                  const float* __restrict__ bo, float* __restrict__ u, int B, int U, int L, float u_scale,
+                                  const int* __restrict__ lens = nullptr) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float Lf = (float)(VL ? od_uniform(lens[b]) : L);
     float s = 0.f;
     for (int c = lane; c < U; c += 64) {
-        const float f = fsum[(size_t)b * U + c] / (float)L;
+        const float f = fsum[(size_t)b * U + c] / Lf;
         s += w[c] * (f * (1.f + mod[(size_t)b * 2 * U + c]) + mod[(size_t)b * 2 * U + U + c]);
     }
     s = od_wave_sum(s);
@@ -380,6 +389,38 @@ __global__ void sampler_eta_kernel(const float* __restrict__ u, float* __restric
     }
 }
 
+// one wave per song g: eta[g][0..1] from the mean of u over rows [offs[g], offs[g+1]), in sampler_eta_kernel's order (lane j <-> row
+// offs[g] + j, then od_wave_sum) — a song's eta is bit for bit the one its own od_sampler_eta computes
+__global__ void sampler_eta_groups_kernel(const float* __restrict__ u, const int* __restrict__ offs, float* __restrict__ eta, float c0,
+                                          int num_steps) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int r0 = od_uniform(offs[g]), n = od_uniform(offs[g + 1]) - r0;
+    float s = 0.f;
+    for (int b = lane; b < n; b += 64) s += u[r0 + b];
+    s = od_wave_sum(s) / (float)n;
+    if (lane == 0) {
+        const float r = sqrtf(c0);
+        const float u0 = s > r + 1e-6f ? s : r + 1e-6f;
+        eta[2 * g] = 1.f - powf(r / u0, 1.f / (float)num_steps);
+        eta[2 * g + 1] = s;
+    }
+}
+
+// x[b] -= eta[g(b)][0] * u[b] * v[b] over frames < lens[b]; frames >= lens[b] of x are written as zero (g(b): offs[g] <= b < offs[g+1])
+__global__ __launch_bounds__(256) void sampler_step_varlen_kernel(float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ v,
+                                                                  const float* __restrict__ eta, const int* __restrict__ lens,
+                                                                  const int* __restrict__ offs, int G, int EL, int L) {
+    const int b = blockIdx.y;
+    int g = 0;
+    while (g + 1 < G && od_uniform(offs[g + 1]) <= b) g++;
+    const int Lb = od_uniform(lens[b]);
+    const float k = eta[2 * g] * u[b];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < EL; i += gridDim.x * 256) {
+        const size_t o = (size_t)b * EL + i;
+        x[o] = (i % L) < Lb ? x[o] - k * v[o] : 0.f;
+    }
+}
+
 }  // namespace
 
 extern "C" int od_uhead_fwd(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
@@ -391,7 +432,22 @@ extern "C" int od_uhead_fwd(const float* xt, const float* w0, const float* b0, c
     // windows a block walks: up to UWPB for long sequences, fewer when that would leave CUs idle (sampler: L ~ 1e3)
     int wpb = (int)((long)nwin * B / 512);
     wpb = wpb < 1 ? 1 : (wpb > UWPB ? UWPB : wpb);
-    OD_LAUNCH(uhead_fwd_kernel, dim3((nwin + wpb - 1) / wpb, B), dim3(256), 0, (hipStream_t)stream, xt, P, fsum, E, L, U, nwin, wpb, od_det_active());
+    OD_LAUNCH(uhead_fwd_kernel<>, dim3((nwin + wpb - 1) / wpb, B), dim3(256), 0, (hipStream_t)stream, xt, P, fsum, E, L, U, nwin, wpb, od_det_active());
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_uhead_fwd_varlen(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
+                                   const float* b3, const float* w4, const float* b4, float* fsum, const int* lens, int B, int E, int L,
+                                   int U, void* stream) {
+    if (U > MAXU || U % 8 || E > MAXE) return OD_ERR_UNSUPPORTED;
+    if (!lens) return OD_ERR_ARG;
+    const int nwin = (L + UOWN - 1) / UOWN;
+    UHeadW P{w0, b0, w1, b1, w3, b3, w4, b4};
+    int wpb = (int)((long)nwin * B / 512);          // the same window split as od_uhead_fwd
+    wpb = wpb < 1 ? 1 : (wpb > UWPB ? UWPB : wpb);
+    OD_LAUNCH(uhead_fwd_kernel<true>, dim3((nwin + wpb - 1) / wpb, B), dim3(256), 0, (hipStream_t)stream, xt, P, fsum, E, L, U, nwin, wpb,
+              od_det_active(), lens);
     OD_CHECK_LAUNCH();
     return 0;
 }
@@ -411,7 +467,15 @@ extern "C" int od_uhead_bwd(const float* xt, const float* w0, const float* b0, c
 
 extern "C" int od_uhead_tail(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, int B, int U,
                              int L, float u_scale, void* stream) {
-    OD_LAUNCH(uhead_tail_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, u, B, U, L, u_scale);
+    OD_LAUNCH(uhead_tail_kernel<>, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, u, B, U, L, u_scale);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_uhead_tail_varlen(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, const int* lens,
+                                    int B, int U, int L, float u_scale, void* stream) {
+    if (!lens) return OD_ERR_ARG;
+    OD_LAUNCH(uhead_tail_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, u, B, U, L, u_scale, lens);
     OD_CHECK_LAUNCH();
     return 0;
 }
@@ -459,6 +523,23 @@ extern "C" int od_sampler_step(float* x, const float* u, const float* v, const f
 
 extern "C" int od_sampler_eta(const float* u, float* eta, int B, float c0, int num_steps, void* stream) {
     OD_LAUNCH(sampler_eta_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, u, eta, B, c0, num_steps);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_sampler_eta_groups(const float* u, const int* offs, float* eta, int G, float c0, int num_steps, void* stream) {
+    if (!offs || G < 1) return OD_ERR_ARG;
+    OD_LAUNCH(sampler_eta_groups_kernel, dim3(G), dim3(64), 0, (hipStream_t)stream, u, offs, eta, c0, num_steps);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_sampler_step_varlen(float* x, const float* u, const float* v, const float* eta, const int* lens, const int* offs, int G,
+                                      int B, int E, int L, void* stream) {
+    if (!lens || !offs || G < 1) return OD_ERR_ARG;
+    const int EL = E * L;
+    int gx = (EL + 255) / 256; if (gx > 256) gx = 256;
+    OD_LAUNCH(sampler_step_varlen_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, u, v, eta, lens, offs, G, EL, L);
     OD_CHECK_LAUNCH();
     return 0;
 }

@@ -149,13 +149,16 @@ __global__ __launch_bounds__(256) void silu_bwd_kernel(const T* __restrict__ x, 
 // thread = 8 channels x a run of RUN frames, sliding a K-tap register window down the frames.
 // RUN = 32 for long sequences (halo re-read 1.125x); short workloads (the sampler's B*L = 4460 frames) use
 // RUN = 4 so the launch still covers the chip (the halo re-reads hit L2).
-template <class T, int KS, int DW_RUN>
+// VL: sequence b is valid for frames < Lb = lens[b] (L stays the stride): taps at frames >= Lb read as zero (the reference's
+// own zero padding at the sequence's end) and outputs at frames >= Lb are written as zero.
+template <class T, int KS, int DW_RUN, bool VL = false>
 __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w,
                                                      const float* __restrict__ bias, T* __restrict__ y, int ldy,
-                                                     int L, int C) {
+                                                     int L, int C, const int* __restrict__ lens = nullptr) {
     constexpr int R = KS / 2;
     const int cg = C / 8;
     const int b = blockIdx.y;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const int cgi = (int)(t % cg);
     const long run = t / cg;
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, in
 #pragma unroll
     for (int j = 0; j < KS - 1; j++) {
         const int l = l0 - R + j;
-        if (l >= 0 && l < L) od_ld8(xb + (size_t)l * ldx, win[j]);
+        if (l >= 0 && l < Lb) od_ld8(xb + (size_t)l * ldx, win[j]);
         else {
 #pragma unroll
             for (int k = 0; k < 8; k++) win[j][k] = 0.f;
@@ -184,7 +187,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, in
         const int l = l0 + i;
         if (l >= L) break;
         const int ln = l + R;
-        if (ln < L) od_ld8(xb + (size_t)ln * ldx, win[KS - 1]);
+        if (ln < Lb) od_ld8(xb + (size_t)ln * ldx, win[KS - 1]);
         else {
 #pragma unroll
             for (int k = 0; k < 8; k++) win[KS - 1][k] = 0.f;
@@ -195,7 +198,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, in
             float s = bv[k];
 #pragma unroll
             for (int j = 0; j < KS; j++) s += wv[k][j] * win[j][k];
-            o[k] = s;
+            o[k] = (VL && l >= Lb) ? 0.f : s;
         }
         od_st8(y + ((size_t)b * L + l) * ldy + c, o);
 #pragma unroll
@@ -562,6 +565,25 @@ extern "C" int od_dwconv(int dtype, const void* x, int ldx, const float* w, cons
     if (ksize == 5) { if (small) DW_GO(5, 4); else DW_GO(5, 32); }
     else if (ksize == 3) { if (small) DW_GO(3, 4); else DW_GO(3, 32); }
     else if (ksize == 7) { if (small) DW_GO(7, 4); else DW_GO(7, 32); }      // radius 3, 4: not a shipped config, same kernel
+    else { if (small) DW_GO(9, 4); else DW_GO(9, 32); }
+#undef DW_GO
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_dwconv_varlen(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, const int* lens,
+                                int B, int L, int C, int ksize, void* stream) {
+    if (C % 8 || ldx % 8 || ldy % 8) return OD_ERR_ALIGN;
+    if (ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9) return OD_ERR_UNSUPPORTED;
+    if (!lens) return OD_ERR_ARG;
+    const bool small = (long)B * (C / 8) * ((L + 31) / 32) < OD_DW_SMALL_THREADS;      // the same RUN choice as od_dwconv
+    const int run = small ? 4 : 32;
+    const long threads = (long)(C / 8) * ((L + run - 1) / run);
+    dim3 grid((unsigned)((threads + 255) / 256), B);
+#define DW_GO(KS_, RUN_) DISPATCH_T(dtype, OD_LAUNCH((dwconv_kernel<T_, KS_, RUN_, true>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, w, bias, (T_*)y, ldy, L, C, lens))
+    if (ksize == 5) { if (small) DW_GO(5, 4); else DW_GO(5, 32); }
+    else if (ksize == 3) { if (small) DW_GO(3, 4); else DW_GO(3, 32); }
+    else if (ksize == 7) { if (small) DW_GO(7, 4); else DW_GO(7, 32); }
     else { if (small) DW_GO(9, 4); else DW_GO(9, 32); }
 #undef DW_GO
     OD_CHECK_LAUNCH();

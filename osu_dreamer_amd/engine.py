@@ -90,6 +90,7 @@ class DenoiserEngine:
         # last backward used: its sticky error word is folded into every optimizer step on the device (attn_status_ptr)
         self._attn_ws_cache: Dict[tuple, "ops.FusedAttnBwdWorkspace"] = {}
         self._attn_ws = None
+        self.varlen = False                 # plan(..., lens=...): the per-sequence-length forward
         # "attention in fp16" (BASELINE configs[4]; Lightning precision 16-mixed in the reference's trainer, model.yml:12): q, k, v reach the
         # attention core as IEEE half and its MFMAs are the f16 ones; everything around it stays bf16.  model.attn_dtype = torch.float16.
         self.attn_f16 = False
@@ -171,18 +172,36 @@ class DenoiserEngine:
         ops.gemm_nt(A, W, bias, C, x3=self.x3)
 
     # ------------------------------------------------------------------ plan / workspace
-    def plan(self, B: int, L: int, Ba: int, dtype: torch.dtype, train: bool, x3: bool = False):
-        """`x3`: run the fp32 forward's MFMA products as 3 bf16 MFMAs (OD_F32X3; no-grad paths only)."""
+    def plan(self, B: int, L: int, Ba: int, dtype: torch.dtype, train: bool, x3: bool = False, lens=None, offs=None):
+        """`x3`: run the fp32 forward's MFMA products as 3 bf16 MFMAs (OD_F32X3; no-grad paths only).
+        `lens` (B ints, 1 <= lens[b] <= L; no-grad only): varlen — row b of the padded (B, L) layout is valid for frames < lens[b], and
+        `pred` runs the varlen kernels wherever frames mix (attention, depthwise convs, the u-head's convs and mean).  `offs` (G + 1 ints):
+        the song boundaries over the rows, for the per-song sampler step size.  Both live in plan-owned device int32 buffers, refreshed by a
+        stream-ordered copy on every call: the lengths are not part of the plan key, so a captured sampler graph of the same shape replays."""
         dev = self.model.arena.data.device
         assert not (x3 and train), "the f32x3 product exists for the forward kernels only"
+        varlen = lens is not None
+        assert not (varlen and train), "the varlen forward exists for no-grad paths only"
         x3 = bool(x3 and dtype == torch.float32)
-        key = (B, L, Ba, dtype, train, dev, x3, getattr(self.model, "attn_dtype", None))
+        ngroups = len(offs) - 1 if offs is not None else 0
+        key = (B, L, Ba, dtype, train, dev, x3, getattr(self.model, "attn_dtype", None), varlen, ngroups)
         if key != self._plan_key:
             self.ws = Workspace(dev)
             self._plan_key = key
             self.generation += 1
             tab = self.ws.get("rope", (L, self.hd // 2, 2), torch.float32)
             ops.rope_table(tab, L, self.hd)
+        self.varlen = varlen
+        if varlen:
+            lens_t = torch.as_tensor(lens).to("cpu", torch.int32)
+            if lens_t.shape != (B,) or int(lens_t.min()) < 1 or int(lens_t.max()) > L:
+                raise ValueError(f"lens must hold B = {B} lengths in [1, {L}]")
+            self.ws.get("vl.lens", (B,), torch.int32).copy_(lens_t)
+            if offs is not None:
+                offs_t = torch.as_tensor(offs).to("cpu", torch.int32)
+                if int(offs_t[0]) != 0 or int(offs_t[-1]) != B or bool((offs_t[1:] <= offs_t[:-1]).any()):
+                    raise ValueError("offs must rise strictly from 0 to B")
+                self.ws.get("vl.offs", (ngroups + 1,), torch.int32).copy_(offs_t)
         self.B, self.L, self.Ba, self.dtype, self.train, self.x3 = B, L, Ba, dtype, train, x3
         self.M, self.Ma = B * L, Ba * L
         self.attn_f16 = getattr(self.model, "attn_dtype", None) == torch.float16
@@ -266,8 +285,12 @@ class DenoiserEngine:
                 qk = qkv
             y = self.lbuf("y", i, (M, dh))
             lse = self.lbuf("lse", i, (B, self.H, L), f32)
-            ops.flash_attn_fwd(qk[:, :dh], qk[:, dh:], self._v_of(qkv), y, lse, B, self.H, L, self.hd,
-                               1.0 / math.sqrt(self.hd), x3=self.x3, q_prescaled=True)
+            if self.varlen:
+                ops.flash_attn_fwd_varlen(qk[:, :dh], qk[:, dh:], self._v_of(qkv), y, lse, self.ws.t["vl.lens"], B, self.H, L, self.hd,
+                                          1.0 / math.sqrt(self.hd), x3=self.x3, q_prescaled=True)
+            else:
+                ops.flash_attn_fwd(qk[:, :dh], qk[:, dh:], self._v_of(qkv), y, lse, B, self.H, L, self.hd,
+                                   1.0 / math.sqrt(self.hd), x3=self.x3, q_prescaled=True)
             ao = self.lbuf("ao", i, (M, D))
             self.plain_gemm(y, self.W(p + "attn.out_proj"), self.P(p + "attn.out_proj.bias"), ao)
             # --- gate + residual of the attention branch and norm + FiLM of the feed-forward branch, one pass
@@ -275,7 +298,7 @@ class DenoiserEngine:
             h2 = self.lbuf("h2", i, (M, D))
             # (OD_FUSE_FILM_DWCONV=1: those two AND the SwiGLU branch's depthwise conv as one kernel — bit-identical, 0.3 ms per step at the
             #  bench shape: profiles/r06q_ab_film_dwconv.txt; large training shapes only: a wave walks 32 frames)
-            fuse_dw = (self.radius > 0 and D <= 512 and x.data_ptr() != x_mid.data_ptr() and x.dtype in (torch.bfloat16, torch.float32)
+            fuse_dw = (self.radius > 0 and not self.varlen and D <= 512 and x.data_ptr() != x_mid.data_ptr() and x.dtype in (torch.bfloat16, torch.float32)
                        and os.environ.get("OD_FUSE_FILM_DWCONV", OD_FUSE_FILM_DWCONV_DEFAULT) == "1")
             if fuse_dw:
                 hdw = self.lbuf("hdw", i, (M, D))
@@ -290,7 +313,11 @@ class DenoiserEngine:
                 pass
             elif self.radius > 0:
                 hdw = self.lbuf("hdw", i, (M, D))
-                ops.dwconv(h2, self.P(p + "ffn.proj_vg.0.weight"), self.P(p + "ffn.proj_vg.0.bias"), hdw, B, L, self.ksize)
+                if self.varlen:
+                    ops.dwconv_varlen(h2, self.P(p + "ffn.proj_vg.0.weight"), self.P(p + "ffn.proj_vg.0.bias"), hdw, self.ws.t["vl.lens"], B, L,
+                                      self.ksize)
+                else:
+                    ops.dwconv(h2, self.P(p + "ffn.proj_vg.0.weight"), self.P(p + "ffn.proj_vg.0.bias"), hdw, B, L, self.ksize)
             else:
                 hdw = h2                                      # radius 0: nn.Identity (swiglu.py:20)
             vg = self.lbuf("vg", i, (M, 2 * Hp))
@@ -316,9 +343,15 @@ class DenoiserEngine:
         # distance head on the raw latent (model.py:99-102)
         fsum = self.buf("fsum", (B, self.U), f32)
         fsum.zero_()
-        ops.uhead_fwd(xt, self._uhead_w(), fsum, self.U)
-        self._det_flush(fsum)
-        ops.uhead_tail(fsum, self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), u, L, self.model.u_scale)
+        if self.varlen:
+            ops.uhead_fwd_varlen(xt, self._uhead_w(), fsum, self.ws.t["vl.lens"], self.U)
+            self._det_flush(fsum)
+            ops.uhead_tail_varlen(fsum, self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), u, self.ws.t["vl.lens"], L,
+                                  self.model.u_scale)
+        else:
+            ops.uhead_fwd(xt, self._uhead_w(), fsum, self.U)
+            self._det_flush(fsum)
+            ops.uhead_tail(fsum, self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), u, L, self.model.u_scale)
 
     def _v_of(self, qkv: torch.Tensor) -> torch.Tensor:
         """The v columns of a layer's qkv buffer as the attention core reads them (attn_f16: the same bytes hold IEEE half)."""

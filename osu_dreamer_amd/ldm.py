@@ -9,7 +9,7 @@ and `save_inference(...)` writes one from three fit checkpoints with the referen
 from __future__ import annotations
 
 from dataclasses import asdict, dataclass, is_dataclass
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -86,6 +86,30 @@ class LDM(nn.Module):
         z = self.diffusion.sample(h, s, num_steps, show_progress=show_progress, x_init=x_init)
         chart, out_labels = self.latent.decode(z, s, skips=skips)
         return chart[..., :L], out_labels
+
+    @torch.no_grad()
+    def sample_many(self, audios: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], num_steps: int, *,
+                    s_init: Optional[Sequence[torch.Tensor]] = None, x_init: Optional[Sequence[torch.Tensor]] = None
+                    ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """`sample` for G songs: audios[g] (72, L_g), labels[g] (B_g, 5) -> one (chart (B_g, 9, L_g), labels (B_g, 5)) pair per song.
+        The audio encoder, the style sampler and the decoder run per song exactly as in `sample`; the denoiser sampler runs once for all
+        songs (DiffusionModel.sample_many).  `s_init[g]` / `x_init[g]` pin song g's starting noise, as in `sample`."""
+        G = len(audios)
+        if G == 0 or len(labels) != G or (s_init is not None and len(s_init) != G) or (x_init is not None and len(x_init) != G):
+            raise ValueError("sample_many needs one audio and one label batch per song (and one s_init / x_init per song when given)")
+        enc = []
+        for g, audio in enumerate(audios):
+            if audio.dim() != 2 or audio.size(0) != A_DIM:
+                raise ValueError(f"audios[{g}] must be ({A_DIM}, L), got {tuple(audio.shape)}")
+            skips, h = self.latent.audio_encoder(pad_to_multiple(audio.to(torch.float32), self.latent.chunk_size)[None])
+            s = self.style.sample(labels[g]) if s_init is None else self.style.sample(labels[g], s_init=s_init[g])
+            enc.append((audio.size(-1), skips, h, s))
+        zs = self.diffusion.sample_many([e[2] for e in enc], [e[3] for e in enc], num_steps, x_init=x_init)
+        out = []
+        for (L, skips, _, s), z in zip(enc, zs):
+            chart, out_labels = self.latent.decode(z, s, skips=skips)
+            out.append((chart[..., :L], out_labels))
+        return out
 
 
 def load_inference(model_path: str, device="cuda") -> LDM:

@@ -269,21 +269,33 @@ class DiffusionModel(nn.Module):
         return t.detach().to(torch.float32).contiguous()
 
     # ---- forward (model.py:105-114) --------------------------------------------------
-    def forward(self, audio: torch.Tensor, style: torch.Tensor, xt: torch.Tensor):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+    def forward(self, audio: torch.Tensor, style: torch.Tensor, xt: torch.Tensor, *, lengths=None):
+        """`lengths` (B ints, optional; no-grad only): row b of the batch is a sequence of lengths[b] frames zero-padded to L — attention, the
+        depthwise convs and the u-head's mean see its own frames only, and frames >= lengths[b] of v come back as zero.  `audio` is then
+        (B, A, L), or (1, A, L) when every row has the same audio."""
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if lengths is not None:
+            if grad:
+                raise RuntimeError("forward(..., lengths=...) has no backward: call it under torch.no_grad()")
+            return self._forward_nograd(audio, style, xt, lengths=lengths)
+        if grad:
             return _DenoiserFn.apply(self, audio, style, xt, *self.parameters())
         return self._forward_nograd(audio, style, xt)
 
-    def _forward_nograd(self, audio, style, xt):
+    def _forward_nograd(self, audio, style, xt, lengths=None):
         audio, style, xt = self._f32c(audio), self._f32c(style), self._f32c(xt)
         B, _, L = xt.shape
         eng, dt = self.engine, self._dtype()
         eng.pack_weights(dt, train=False, x3=self._x3())
-        eng.plan(B, L, audio.shape[0], dt, train=False, x3=self._x3())
+        lens = None if lengths is None else [int(n) for n in lengths]
+        eng.plan(B, L, audio.shape[0], dt, train=False, x3=self._x3(), lens=lens)
         eng.conditioning(audio, style)
         u = torch.empty(B, dtype=torch.float32, device=xt.device)
         v = torch.empty_like(xt)
         eng.pred(xt, u, v)
+        if lens is not None:
+            for b, n in enumerate(lens):
+                v[b, :, n:].zero_()
         return u, v
 
     # ---- sampler (model.py:117-138) -----------------------------------------------------
@@ -340,6 +352,92 @@ class DiffusionModel(nn.Module):
             for _ in steps:
                 step()
         return xs.clone()
+
+    @torch.no_grad()
+    def sample_many(self, audios: List[torch.Tensor], styles: List[torch.Tensor], num_steps: int, *,
+                    x_init: Optional[List[torch.Tensor]] = None, show_progress: bool = False) -> List[torch.Tensor]:
+        """`sample` for G songs of different lengths in one batched call.  audios[g]: (1, A, L_g), styles[g]: (B_g, S), x_init[g] (optional):
+        (B_g, E, L_g).  Returns one (B_g, E, L_g) tensor per song.  The songs' rows are stacked and zero-padded to Lpad = ceil64(max L_g)
+        (songs of similar lengths share a plan and a captured graph); the varlen forward keeps every song to its own frames, and the step
+        size eta is computed per song, as its own `sample()` would.  last_sample_stats: (G, 2)."""
+        G = len(audios)
+        if G == 0 or len(styles) != G or (x_init is not None and len(x_init) != G):
+            raise ValueError("sample_many needs one audio and one style batch per song (and one x_init per song when given)")
+        audios = [self._f32c(a) for a in audios]
+        styles = [self._f32c(s) for s in styles]
+        dev, E = audios[0].device, self.emb_dim
+        Ls = [a.shape[-1] for a in audios]
+        Bs = [s.shape[0] for s in styles]
+        for a in audios:
+            if a.dim() != 3 or a.shape[0] != 1:
+                raise ValueError(f"audios[g] must be (1, A, L_g), got {tuple(a.shape)}")
+        Lpad = (max(Ls) + 63) // 64 * 64
+        B = sum(Bs)
+        offs = [0]
+        for n in Bs:
+            offs.append(offs[-1] + n)
+        lens = [Ls[g] for g in range(G) for _ in range(Bs[g])]
+        # the audio, one row per style row (one song: broadcast as in sample()) — loop-invariant, once per call
+        Ba = 1 if G == 1 else B
+        audio = torch.zeros(Ba, audios[0].shape[1], Lpad, device=dev)
+        x = torch.zeros(B, E, Lpad, device=dev)
+        for g in range(G):
+            r0, r1, Lg = offs[g], offs[g + 1], Ls[g]
+            audio[0 if G == 1 else slice(r0, r1), :, :Lg] = audios[g][0]
+            xg = torch.randn(Bs[g], E, Lg, device=dev) if x_init is None else self._f32c(x_init[g])
+            if tuple(xg.shape) != (Bs[g], E, Lg):
+                raise ValueError(f"x_init[{g}] must be ({Bs[g]}, {E}, {Lg}), got {tuple(xg.shape)}")
+            x[r0:r1, :, :Lg] = xg
+        style = torch.cat(styles, 0)
+        eng, dt = self.engine, self._dtype()
+        eng.pack_weights(dt, train=False, x3=self._x3())
+        eng.plan(B, Lpad, Ba, dt, train=False, x3=self._x3(), lens=lens, offs=offs)
+        eng.conditioning(audio, style)
+        lens_d, offs_d = eng.ws.t["vl.lens"], eng.ws.t["vl.offs"]
+        u = eng.buf("smp.u", (B,), torch.float32)
+        v = eng.buf("smp.v", (B, E, Lpad), torch.float32)
+        eta = eng.buf("smp.eta_g", (G, 2), torch.float32)
+        xs = eng.buf("smp.x", (B, E, Lpad), torch.float32)
+        xs.copy_(x)
+        eng.pred(xs, u, v)
+        ops.sampler_eta_groups(u, offs_d, eta, self.c0, num_steps)
+        self.last_sample_stats = eta
+
+        def step():
+            eng.pred(xs, u, v)
+            ops.sampler_step_varlen(xs, u, v, eta, lens_d, offs_d)
+
+        self._run_steps(step, num_steps, dev, show_progress)
+        return [xs[offs[g]:offs[g + 1], :, :Ls[g]].clone() for g in range(G)]
+
+    def _run_steps(self, step, num_steps: int, dev, show_progress: bool):
+        """The sampler loop of sample_many: hipGraph-captured under sample()'s rules (one slot, keyed by the plan — whose key carries the
+        varlen flag — the packed weights, their generation and the deterministic mode); the lengths are device data, not part of the key.
+        (sample() keeps its own copy of this loop, unchanged.)"""
+        eng = self.engine
+        steps = range(num_steps)
+        if show_progress:
+            try:
+                import tqdm
+                steps = tqdm.trange(num_steps)
+            except ImportError:
+                pass
+        if self.use_graph and dev.type == "cuda" and num_steps > 1 and not eng._drop_active():
+            from .graph import CapturedLoop
+            from . import det
+            key = (eng._plan_key, eng._packed_key, eng.generation, det.enabled())
+            if self._graph is None or self._graph[0] != key:
+                if self._graph is not None:
+                    self._graph[1].close()
+                self._graph = (key, CapturedLoop(step, dev))
+            loop = self._graph[1]
+            loop.begin()
+            for _ in steps:
+                loop.replay()
+            loop.end()
+        else:
+            for _ in steps:
+                step()
 
 
 class _DenoiserFn(torch.autograd.Function):

@@ -65,6 +65,11 @@ def _f32(*ts):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "expected contiguous fp32"
 
 
+def _i32(*ts):
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_contiguous(), "expected contiguous int32"
+
+
 # ---------------------------------------------------------------- GEMMs
 def gemm_nt(A, W, bias, C, epilogue=OD_EPI_NONE, accumulate=False, x3=False):
     code, W = mm_code(A.dtype, x3, W), _w(W)
@@ -280,6 +285,16 @@ class AttnAux:
             pass
 
 
+def flash_attn_fwd_varlen(q, k, v, o, lse, lens, B, H, L, hd, scale, x3=False, q_prescaled=False):
+    """flash_attn_fwd per sequence: lens (device int32 [B]) = valid rows of each sequence of the padded (B, L) layout.
+    Rows >= lens[b] of o and lse come back as 0."""
+    _f32(lse)
+    _i32(lens)
+    assert q.dtype == k.dtype == v.dtype and (o.dtype == q.dtype or (q.dtype == torch.float16 and o.dtype == torch.bfloat16))
+    _lib.lib().od_flash_attn_fwd_varlen(mm_code(q.dtype, x3), _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(o), _ld(o), _p(lse),
+                                        _p(lens), B, H, L, hd, scale, int(q_prescaled), _stream(q))
+
+
 def flash_attn_bwd(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, L, hd, scale, q_prescaled=False, aux=None):
     _f32(lse, delta)
     _lib.lib().od_flash_attn_bwd_aux(dt_code(q.dtype), _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(o), _ld(o), _p(do),
@@ -344,6 +359,14 @@ def dwconv(x, w, bias, y, B, L, ksize):
     _lib.lib().od_dwconv(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, L, C, ksize, _stream(x))
 
 
+def dwconv_varlen(x, w, bias, y, lens, B, L, ksize):
+    """dwconv per sequence of valid length lens[b] (device int32 [B]); frames >= lens[b] of y come back as 0."""
+    C = x.shape[1]
+    _f32(w, bias)
+    _i32(lens)
+    _lib.lib().od_dwconv_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, L, C, ksize, _stream(x))
+
+
 def dwconv_bwd(x, w, dy, dx, dw, db, B, L, ksize):
     C = x.shape[1]
     _f32(w, dw, db)
@@ -394,6 +417,13 @@ def uhead_fwd(xt, w, fsum, U):
     _lib.lib().od_uhead_fwd(_p(xt), *[_p(t) for t in w], _p(fsum), B, E, L, U, _stream(xt))
 
 
+def uhead_fwd_varlen(xt, w, fsum, lens, U):
+    B, E, L = xt.shape
+    _f32(xt, fsum, *w)
+    _i32(lens)
+    _lib.lib().od_uhead_fwd_varlen(_p(xt), *[_p(t) for t in w], _p(fsum), _p(lens), B, E, L, U, _stream(xt))
+
+
 def uhead_bwd(xt, w, dfm, g, U):
     B, E, L = xt.shape
     _f32(xt, dfm, *w, *g)
@@ -404,6 +434,13 @@ def uhead_tail(fsum, mod, w_out, b_out, u, L, u_scale):
     B, U = fsum.shape
     _f32(fsum, mod, w_out, b_out, u)
     _lib.lib().od_uhead_tail(_p(fsum), _p(mod), _p(w_out), _p(b_out), _p(u), B, U, L, u_scale, _stream(fsum))
+
+
+def uhead_tail_varlen(fsum, mod, w_out, b_out, u, lens, L, u_scale):
+    B, U = fsum.shape
+    _f32(fsum, mod, w_out, b_out, u)
+    _i32(lens)
+    _lib.lib().od_uhead_tail_varlen(_p(fsum), _p(mod), _p(w_out), _p(b_out), _p(u), _p(lens), B, U, L, u_scale, _stream(fsum))
 
 
 def uhead_tail_bwd(fsum, mod, w_out, b_out, du, dfm, dmod, dw_out, db_out, L, u_scale):
@@ -441,6 +478,22 @@ def sampler_step(x, u, v, eta):
 def sampler_eta(u, eta, c0, num_steps):
     _f32(u, eta)
     _lib.lib().od_sampler_eta(_p(u), _p(eta), u.shape[0], c0, num_steps, _stream(u))
+
+
+def sampler_eta_groups(u, offs, eta, c0, num_steps):
+    """eta (G, 2): per song g, sampler_eta over rows [offs[g], offs[g+1]) of u (offs: device int32 [G+1])."""
+    _f32(u, eta)
+    _i32(offs)
+    G = offs.shape[0] - 1
+    assert eta.numel() >= 2 * G
+    _lib.lib().od_sampler_eta_groups(_p(u), _p(offs), _p(eta), G, c0, num_steps, _stream(u))
+
+
+def sampler_step_varlen(x, u, v, eta, lens, offs):
+    B, E, L = x.shape
+    _f32(x, u, v, eta)
+    _i32(lens, offs)
+    _lib.lib().od_sampler_step_varlen(_p(x), _p(u), _p(v), _p(eta), _p(lens), _p(offs), offs.shape[0] - 1, B, E, L, _stream(x))
 
 
 # ---------------------------------------------------------------- optimizer
