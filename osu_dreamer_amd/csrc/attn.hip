@@ -719,9 +719,6 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
     }
 }
 
-#ifndef OD_FWD16X
-#define OD_FWD16X 1       // bf16 / IEEE-half operands, hd 64, pre-multiplied q: flash_fwd16x_kernel — flash_fwd32_kernel's structure on 16x16x32 tiles (0: flash_fwd32_kernel)
-#endif
 #ifndef OD_FWD16X_NQT
 #define OD_FWD16X_NQT 2   // 16-query tiles per wave (4: a tie, 7.39-7.48 ms; 1: 8.87; 3: 7.85 — profiles/r06h_ab_fwd16x_nqt_sampler.txt)
 #endif
@@ -731,7 +728,6 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
 #ifndef OD_FWD16X_MIN_L
 #define OD_FWD16X_MIN_L 2048   // sequences from this length on run flash_fwd16x_kernel, shorter ones flash_fwd32_kernel (the emulator build lowers it: both are tested)
 #endif
-#if OD_FWD16X
 // flash_fwd32_kernel's STRUCTURE — buffer-addressed asm LDS-DMA (rows past L read as zero), compile-time stage addresses (loop unrolled by two),
 // the lazy log2-domain reference with the running row SUM as the overflow guard (no per-tile row maximum), scalar row sums — on
 // v_mfma_f32_16x16x32 tiles in flash_fwd_kernel's formulation (S^T = K Q^T: a softmax row is an accumulator column; P^T feeds O^T += V^T P^T
@@ -905,7 +901,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
         }
     }
 }
-#endif
 
 // (An 8-wave ping-pong arrangement of this kernel — two wave groups alternating MFMA and softmax phases behind bare barriers, K/V in a
 // 4-deep LDS ring — measured 8.36 ms against 7.9-8.1 and was removed: profiles/r02g_ab_pingpong.txt.)
@@ -1248,7 +1243,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 ? 3 : 2)) void flash_bwd_dq_kerne
 }
 
 // (The 32x32x16-MFMA form of the dQ kernel, the norm + RoPE backward in the dQ / dK epilogues, the interleaved-chain and 8-wave dK/dV variants and the
-// timing-only modes of rounds 2-3 live in variants/attn_r03_variants.hip: tools/build_variant.sh compiles that file in place of this one on demand.)
+// timing-only modes of rounds 2-3 were removed with attn_r03_variants.hip; git history holds them: git log --all -- '*attn_r03_variants.hip'.)
 
 #ifndef OD_ATTN_NW
 #define OD_ATTN_NW 4      // waves per workgroup of the bf16 forward / dQ kernels.  6 (K/V streamed once per 192 queries) measured 0.71x: a 6-wave group lands 2,2,1,1 on the SIMDs and a second group no longer fits at 3 waves/SIMD
@@ -1257,9 +1252,6 @@ __global__ __launch_bounds__(64 * NW, (NW >= 6 ? 3 : 2)) void flash_bwd_dq_kerne
 #define OD_FWD_NQT1_BELOW 2048  // fp32 forward, head_dim 64: 16 queries per wave when the 32-query grid has fewer workgroups than this (0 = never).  At the sampler's size
                                 // (576 workgroups = 1.09 rounds of the chip run as two) the fp32 call goes 293.5 -> 287.3 ms; the fp32-bf16x3 product, whose hi / lo fragment
                                 // split is amortised over half the MFMAs then, 155.5 -> 170.8 ms: fp32 only
-#endif
-#ifndef OD_FWD32
-#define OD_FWD32 1        // bf16, head_dim 64: the 32x32x16 kernel (0 = the 16x16x32 kernel, kept for A/B and for hd 32 / fp32)
 #endif
 #ifndef OD_FWD32_NQB
 #define OD_FWD32_NQB 1    // 32-query blocks per wave
@@ -1279,7 +1271,6 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
                int H, int L, float scale, hipStream_t st, const int* lens = nullptr) {
     if constexpr (std::is_same<T, f16_t>::value) {          // half operands: q, k, v are IEEE half, o is written as bf16 (head_dim 64 only)
         static_assert(HD == 64, "the half-operand forward exists for head_dim 64");
-#if OD_FWD16X
         static const int fwd16x_min_l_h = od_env_int("OD_FWD16X_MIN_L", OD_FWD16X_MIN_L);
         if (PRE && L >= fwd16x_min_l_h) {
             constexpr int NQT = OD_FWD16X_NQT;
@@ -1289,7 +1280,6 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
             OD_CHECK_LAUNCH();
             return 0;
         }
-#endif
         constexpr int NW = 4, NQB = OD_FWD32_NQB;
         const int grid = attn_grid((L + NW * NQB * 32 - 1) / (NW * NQB * 32), B * H);
         OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE, f16_t, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<bf16_t, HD>::BYTES), st, (const bf16_t*)q, ldq,
@@ -1300,7 +1290,6 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
 #ifndef OD_FWD32_NW
 #define OD_FWD32_NW 4     // waves per workgroup of the bf16 / hd 64 forward (8: one workgroup per CU, the K / V tiles staged once for 256 queries; A/B)
 #endif
-#if OD_FWD16X
     // long sequences: the 16x16x32 form (7.48 against 7.80 ms at B = 32 x L = 8192); at the sampler's L = 1115 the 32x32x16 form is ahead by 1.5 %
     // (66.7 against 65.7 ms per 50-step call: profiles/r06h_ab_fwd16x_nqt_sampler.txt).  OD_FWD16X_MIN_L moves the switch.
     static const int fwd16x_min_l = od_env_int("OD_FWD16X_MIN_L", OD_FWD16X_MIN_L);
@@ -1314,28 +1303,24 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
         return 0;
       }
     }
-#endif
-    if constexpr (OD_FWD32 && std::is_same<T, bf16_t>::value && HD == 64) {
+    if constexpr (std::is_same<T, bf16_t>::value && HD == 64) {
         constexpr int NW = OD_FWD32_NW, NQB = OD_FWD32_NQB;
         const int grid = attn_grid((L + NW * NQB * 32 - 1) / (NW * NQB * 32), B * H);
         OD_LAUNCH_DYN((flash_fwd32_kernel<NW, NQB, PRE, bf16_t, VL>), dim3(grid), dim3(64 * NW), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
                       (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
-    }
-#ifndef OD_FWD_X3P
-#define OD_FWD_X3P 1      // fp32-as-3-x-bf16, head_dim 64: the kernel that splits K / V once per tile at staging time (0 = the generic kernel, for A/B)
-#endif
+    } else if constexpr (std::is_same<T, f32x3_t>::value && HD == 64) {
+        // fp32-as-3-x-bf16: the kernel that splits K / V once per tile at staging time
 #ifndef OD_X3P_NQT
 #define OD_X3P_NQT 2      // 16-query tiles per wave of the fp32-as-3-x-bf16 forward (1: A/B, profiles/r06l_ab_x3p_nqt.txt)
 #endif
-    if constexpr (OD_FWD_X3P && std::is_same<T, f32x3_t>::value && HD == 64) {
         const int grid = attn_grid((L + 4 * 16 * OD_X3P_NQT - 1) / (4 * 16 * OD_X3P_NQT), B * H);
         OD_LAUNCH_DYN((flash_fwd_x3p_kernel<4, PRE, OD_X3P_NQT, VL>), dim3(grid), dim3(256), (2 * 4 * 64 * 128), st, (const float*)q, ldq, (const float*)k, ldk,
                       (const float*)v, ldv, (float*)o, ldo, lse, B, H, L, scale, lens);
         OD_CHECK_LAUNCH();
         return 0;
-    }
+    } else {
     constexpr int NW = Stage<T, HD>::TR ? OD_ATTN_NW : 4;
     // fp32: 16 queries per wave when the 32-query grid is only a few rounds of the chip (sampler sizes): half-size waves quantise better
     static const int nqt1_below = od_env_int("OD_FWD_NQT1_BELOW", OD_FWD_NQT1_BELOW);       // workgroups of the 32-query form
@@ -1353,6 +1338,7 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
     OD_CHECK_LAUNCH();
     return 0;
     }
+    }
 }
 
 template <class T, int HD, int NK, int NQ, bool PRE>
@@ -1366,8 +1352,7 @@ int launch_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
     // workgroups fill the CUs the other kernel's last block round leaves idle: 24.69 -> 24.43 ms per layer (profiles/r03h_ab_bwd_two_streams.txt).
     hipStream_t st_q = st;
 #if !defined(OD_EMU)
-    static const int two_streams = od_env_int("OD_BWD_2STREAM", 1);      // 0: ignore the side stream (A/B)
-    if (aux && two_streams) {
+    if (aux) {
         // a side stream that cannot be forked into (another device's, a destroyed one) is not an error of this call: run single-stream
         if (hipEventRecord(aux->fork, st) == hipSuccess && hipStreamWaitEvent(aux->side, aux->fork, 0) == hipSuccess) st_q = aux->side;
         else (void)hipGetLastError();
@@ -1428,12 +1413,6 @@ extern "C" int od_flash_attn_fwd_varlen(int dtype, const void* q, int ldq, const
     return OD_ERR_UNSUPPORTED;
 }
 
-#ifndef OD_BWD_NK
-#define OD_BWD_NK 3
-#endif
-#ifndef OD_BWD_NQ
-#define OD_BWD_NQ 4
-#endif
 extern "C" int od_flash_attn_bwd_passes(void) { return 7; }   // dK/dV kernel: S, dP, dV, dK; dQ kernel: S, dP, dQ
 
 extern "C" int od_attn_aux_create(void** aux_out) {

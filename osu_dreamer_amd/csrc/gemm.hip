@@ -24,9 +24,6 @@ namespace {
 #ifndef OD_GEMM_BIG_MIN_M
 #define OD_GEMM_BIG_MIN_M 32768   // rows from which the 256x256 kernels are used
 #endif
-#ifndef OD_NT_BIG_MIN_TILES
-#define OD_NT_BIG_MIN_TILES 0     // (see launch_nt)
-#endif
 
 constexpr int BM = 128, BN = 128;
 constexpr int STAGE_BYTES = 32768;  // A 16 KiB + B 16 KiB
@@ -130,12 +127,10 @@ __device__ __forceinline__ bool tn_map_row(const TnRowMap rm, int n, int N, int&
 // launches whose 128-row tiling would leave CUs idle: the sampler's M = B*L = 4460 against N = 512)
 // LDS stages of gemm_nt_kernel and its dynamic LDS size.  At the sampler's sizes (M = 4460: one workgroup per CU, 16-44 k-tiles of ~0.15 us of
 // MFMAs each) an iteration of the two-stage loop lasts one fetch latency (~1 us); with three stages two fetches are in flight.
-#ifndef OD_GEMM_NT_STAGES3
-#define OD_GEMM_NT_STAGES3 2       // 1: three stages for every type at WMT <= 2; 2: not for plain fp32; 0: never
-#endif
+// Three stages at WMT <= 2 for every type but plain fp32.
 template <class T, bool DMA, int WMT>
 constexpr int gemm_nt_stages() {
-    return (DMA && (WMT <= 2 || OD_GEMM_NT_STAGES3 == 3) && (OD_GEMM_NT_STAGES3 == 1 || (OD_GEMM_NT_STAGES3 >= 2 && !std::is_same<T, float>::value))) ? 3 : 2;
+    return (DMA && WMT <= 2 && !std::is_same<T, float>::value) ? 3 : 2;
 }
 template <class T, bool DMA, int WMT>
 constexpr int gemm_nt_smem_bytes() {
@@ -547,9 +542,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_big_kernel(const T* __restrict
 // A fetch has 0.7 - 1.4 tile times to land.  asm MFMAs with "a" constraints keep the 256 accumulators in AGPRs (the builtin form compiled
 // to ~6 v_accvgpr copies per MFMA); LDS-DMA through a buffer descriptor (rows past M / N read as zero; past the last tile the
 // descriptor has length 0: no fetch, same wait counts).  bf16, K % 128 == 0, N % 8 == 0.
-#ifndef OD_W4_PIN
-#define OD_W4_PIN 1
-#endif
 #ifndef OD_W4_R_AT
 #define OD_W4_R_AT 32          // RELEASE barrier in front of this MFMA; the slab-1 reads sit in front of MFMAs 0, 2, .. below it
 #endif
@@ -561,12 +553,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_big_kernel(const T* __restrict
 #endif
 #ifndef OD_W4_DMA_EVERY
 #define OD_W4_DMA_EVERY 6
-#endif
-#ifndef OD_W4_X
-#define OD_W4_X 0          // timing experiments only (wrong results): 2 no loop fragment reads, 4 no loop barriers, 8 no loop waits, 16 no fetch
-#endif
-#ifndef OD_W4_STAGGER
-#define OD_W4_STAGGER 0
 #endif
 template <int EPI>
 __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W, int ldw,
@@ -594,14 +580,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
     const int wm = wave >> 1, wn = wave & 1;
     const int x = lane & 15, g = lane >> 4;
     const int nk = K / 64;
-#if OD_W4_STAGGER && !defined(OD_EMU)
-    // A/B (round 6): every second workgroup of an XCD starts OD_W4_STAGGER x ~4 us late, so that the store bursts of the epilogues (all
-    // workgroups walk tiles of equal length) do not fall on top of each other
-    if ((blockIdx.x >> 3) & 1) {
-#pragma unroll 1
-        for (int i = 0; i < OD_W4_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
 
     // The accumulators START at the bias: lane (x, g) holds, for output row m0 + wm*128 + 16 j + x, the columns n0 + wn*128 + 32 p + 8 g .. + 7
     // (acc[2p][j][0..3], acc[2p+1][j][0..3]) — the same eight bias values for every j.  (A bias load in the epilogue would sit behind the
@@ -678,11 +656,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
     auto rd_seq = [&](const unsigned char* st, int sl, int r) {
         if (r == 0) rdW(st, sl, 0); else if (r < 9) rdA(st, sl, r - 1); else rdW(st, sl, r - 8);
     };
-#if OD_W4_PIN
-#define W4_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define W4_FENCE() ((void)0)
-#endif
 
     // prologue: tiles 0 and 1 in flight, tile 0 landed, its slab-0 fragments in register set 0
 #pragma unroll
@@ -708,32 +681,27 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
 #pragma clang loop unroll(full)
         for (int n = 0; n < 128; n++) {
             if (n == OD_W4_R_AT) {
-                if (!(OD_W4_X & 8)) OD_WAIT_LGKMCNT(0);
-                if (!(OD_W4_X & 4)) od_barrier_raw();
+                OD_WAIT_LGKMCNT(0);
+                od_barrier_raw();
                 srd = wrap ? srd_nxt : srd_cur;
-                if (OD_W4_X & 16) od_srd_set_bytes(srd, 0u);
             }
             if (n == OD_W4_L_AT) {
-                if (!(OD_W4_X & 8)) {
 #define W4_VM(c) else if (BEFORE_L == c) OD_WAIT_VMCNT(c)
-                    if (BEFORE_L >= 16) OD_WAIT_VMCNT(16);
-                    W4_VM(15); W4_VM(14); W4_VM(13); W4_VM(12); W4_VM(11); W4_VM(10); W4_VM(9); W4_VM(8); W4_VM(7); W4_VM(6); W4_VM(5); W4_VM(4);
-                    else OD_WAIT_VMCNT(0);
+                if (BEFORE_L >= 16) OD_WAIT_VMCNT(16);
+                W4_VM(15); W4_VM(14); W4_VM(13); W4_VM(12); W4_VM(11); W4_VM(10); W4_VM(9); W4_VM(8); W4_VM(7); W4_VM(6); W4_VM(5); W4_VM(4);
+                else OD_WAIT_VMCNT(0);
 #undef W4_VM
-                }
-                if (!(OD_W4_X & 4)) od_barrier_raw();
+                od_barrier_raw();
             }
             const bool d = n >= DMA0 && (n - DMA0) % OD_W4_DMA_EVERY == 0 && (n - DMA0) / OD_W4_DMA_EVERY < 16;
             const int q = (n - DMA0) / OD_W4_DMA_EVERY;
             if (d) od_dma_set_dst(dst + (unsigned)q * 1024u);
-            if (!(OD_W4_X & 2)) {
-                // 16 reads in front of MFMAs 0, 1, 3, 4, 6, ... (two per three) of the first OD_W4_RD1_BY: the last one is well ahead of the barrier
-                if (n < OD_W4_RD1_BY && (n % 3 != 2) && (n / 3) * 2 + n % 3 < 16) rd_seq(X, 1, (n / 3) * 2 + n % 3);
-                if (n >= OD_W4_L_AT && (n - OD_W4_L_AT) % 2 == 0 && (n - OD_W4_L_AT) / 2 < 16) rd_seq(Y, 0, (n - OD_W4_L_AT) / 2);
-            }
+            // 16 reads in front of MFMAs 0, 1, 3, 4, 6, ... (two per three) of the first OD_W4_RD1_BY: the last one is well ahead of the barrier
+            if (n < OD_W4_RD1_BY && (n % 3 != 2) && (n / 3) * 2 + n % 3 < 16) rd_seq(X, 1, (n / 3) * 2 + n % 3);
+            if (n >= OD_W4_L_AT && (n - OD_W4_L_AT) % 2 == 0 && (n - OD_W4_L_AT) / 2 < 16) rd_seq(Y, 0, (n - OD_W4_L_AT) / 2);
             mma_one(n >> 6, n & 63);
             if (d) od_buffer_lds16_m0(srd, voff4[q & 3], so + (unsigned)(q >> 2) * 4u * piece_stride);
-            W4_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
     for (int v = 0;; v++) {
@@ -793,22 +761,14 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
                         }
                         acc[4 * hq + 2 * p][j] = bv[4 * hq + 2 * p]; acc[4 * hq + 2 * p + 1][j] = bv[4 * hq + 2 * p + 1];
                     }
-#ifndef OD_W4Q_LINE_STORES
-#define OD_W4Q_LINE_STORES 0     // 1: whole 128-byte lines here too (od_store_line_pair) — measured SLOWER in this VALU-heavy epilogue (1.33 against 1.25 ms)
-#endif
-                    const int row16 = m0 + wm * 128 + j * 16;
-                    const bool cols_ok = hc0 < N;
+                    // (whole 128-byte lines per store, as below, measured slower in this VALU-heavy epilogue: 1.33 against 1.25 ms)
                     T* crow = C + (size_t)(valid ? gm : 0) * ldc + hc0 + 8 * g;
                     if (!roped && rp.f16) {                   // v as IEEE half, straight from the accumulators (no bf16 rounding in between)
-                        if (OD_W4Q_LINE_STORES) od_store_line_pair<f16_t, false>((f16_t*)C + hc0, (size_t)ldc, row16, x, g, M, cols_ok, raw[0], raw[1]);
-                        else if (valid) { od_st8((f16_t*)crow, raw[0]); od_st8((f16_t*)crow + 32, raw[1]); }
+                        if (valid) { od_st8((f16_t*)crow, raw[0]); od_st8((f16_t*)crow + 32, raw[1]); }
                         continue;
                     }
                     if (!roped || qk) {
-                        if (OD_W4Q_LINE_STORES) {
-                            if (c_nt) od_store_line_pair<T, true>(C + hc0, (size_t)ldc, row16, x, g, M, cols_ok, v[0], v[1]);
-                            else od_store_line_pair<T, false>(C + hc0, (size_t)ldc, row16, x, g, M, cols_ok, v[0], v[1]);
-                        } else if (valid) {
+                        if (valid) {
                             if (c_nt) { od_st8_nt(crow, v[0]); od_st8_nt(crow + 32, v[1]); }
                             else { od_st8(crow, v[0]); od_st8(crow + 32, v[1]); }
                         }
@@ -829,11 +789,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
                     }
                     // (stored non-temporally the q, k stream takes a third off the kernel's fabric reads and nothing off the step:
                     // profiles/r05b_qkrope_fetch.txt)
-                    if (OD_W4Q_LINE_STORES) {
-                        if (rp.f16 && qk) od_store_line_pair<f16_t, false>((f16_t*)qk + hc0, (size_t)rp.ldqk, row16, x, g, M, cols_ok, o0, o1);
-                        else if (qk) od_store_line_pair<T, false>(qk + hc0, (size_t)rp.ldqk, row16, x, g, M, cols_ok, o0, o1);
-                        else od_store_line_pair<T, false>(C + hc0, (size_t)ldc, row16, x, g, M, cols_ok, o0, o1);
-                    } else if (valid) {
+                    if (valid) {
                         T* dst = qk ? qk + (size_t)gm * rp.ldqk + hc0 + 8 * g : crow;
                         if (rp.f16 && qk) { od_st8((f16_t*)dst, o0); od_st8((f16_t*)dst + 32, o1); }
                         else { od_st8(dst, o0); od_st8(dst + 32, o1); }
@@ -841,10 +797,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
                 }
             }
         } else {
-#ifndef OD_W4_LINE_STORES
-#define OD_W4_LINE_STORES 1     // 0: the round-3 epilogue (two 64-byte row segments per line, from two store instructions); A/B
-#endif
-#if OD_W4_LINE_STORES
         // Whole 128-byte lines per store instruction.  A lane holds, of row 16 j + x, the columns 32 p + 8 g .. + 7 (16 bytes): the four g lanes
         // of a row cover 64 bytes, and the second half of that line belongs to p + 1 — another instruction, written some microseconds later, so
         // the memory system saw two partial-line writes per line (every K = 512 product wrote at the same 1.85 TB/s: profiles/r05_ab_records.txt).
@@ -878,10 +830,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
                 const int gm_lo = m0 + wm * 128 + j * 16 + xr, gm_hi = gm_lo + 8;
                 // rows 8..15: lanes x >= 8 write their OWN p = 2 pp piece at the line's first half, lanes x < 8 the partner's p = 2 pp + 1 piece
                 const int gn_hi = n0 + wn * 128 + 64 * pp + 32 * (1 - xh) + 8 * g;
-                // (OD_W4_X & 32, timing only: every second workgroup of an XCD keeps its results in registers — does a CU's store phase get
-                // shorter when half the chip is silent?  profiles/r06d_nt_store_contention.txt)
-                const bool silent = (OD_W4_X & 32) && ((blockIdx.x >> 3) & 1);
-                if (silent) { asm volatile("" :: "v"(lo), "v"(hi)); continue; }
                 if (gn < N && gm_lo < M) {
                     T* dst = C + (size_t)gm_lo * ldc + gn;
                     if (nt_store) od_st16_nt(dst, lo); else *(u32x4*)dst = lo;
@@ -892,27 +840,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
                 }
             }
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int gm = m0 + wm * 128 + j * 16 + x;
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                const int gn = n0 + wn * 128 + 32 * p + 8 * g;
-                float v8[8];
-#pragma unroll
-                for (int r = 0; r < 4; r++) { v8[r] = acc[2 * p][j][r]; v8[4 + r] = acc[2 * p + 1][j][r]; }
-                acc[2 * p][j] = bv[2 * p]; acc[2 * p + 1][j] = bv[2 * p + 1];
-                if (gm >= M || gn >= N) continue;
-                T* dst = C + (size_t)gm * ldc + gn;
-                if (EPI == OD_EPI_SILU) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) v8[e] = od_silu(v8[e]);
-                }
-                if (nt_store) od_st8_nt(dst, v8); else od_st8(dst, v8);
-            }
-        }
-#endif
         }
         if (!more) break;
 #if !defined(OD_EMU)
@@ -920,7 +847,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(const bf16_t* __rest
 #endif
         m0 = m1; n0 = n1; srd_cur = srd_nxt;
     }
-#undef W4_FENCE
     OD_WAIT_VMCNT(0);
 }
 
@@ -1137,9 +1063,9 @@ __device__ __forceinline__ void tn512_frag(od_frag<bf16_t>& f, const unsigned ch
 // step's four shapes (profiles/r05_ab_records.txt).  Tile -> (n0, k0, M-split) maps (block b runs on XCD b % 8):
 //   packed (xcd_order 2): the (split, tile) items, split-major, are cut into 8 consecutive runs, one per XCD, so the tiles of one M-split — which
 //     stream the same G / A rows — sit on ONE XCD and share them through its L2, with the FEWEST M-splits that fill the chip (every split costs
-//     N x K fp32 atomics in the epilogue: at 340 G atomics/s chip-wide a workgroup's 65,536 take ~49 us).  The default on every shape.
-//   XCD-aware (1): all output tiles of one M-split side by side on one XCD, M-splits = 8 k (round 2; OD_TN_PACK=1 brings it back for >= 16 tiles).
-//   plain (0): tile index fastest.
+//     N x K fp32 atomics in the epilogue: at 340 G atomics/s chip-wide a workgroup's 65,536 take ~49 us).  The order launch_tn uses.
+//   XCD-aware (1): all output tiles of one M-split side by side on one XCD, M-splits = 8 k (round 2; no longer launched).
+//   plain (0): tile index fastest (no longer launched).
 // every lambda of the kernel must be inlined: one that is not keeps its by-reference captures (the 256 accumulators!) in scratch memory
 #if defined(OD_EMU)
 #define TNW4_INLINE
@@ -1151,9 +1077,6 @@ __device__ __forceinline__ void tn512_frag(od_frag<bf16_t>& f, const unsigned ch
 #endif
 #ifndef OD_TNW4_L_AT
 #define OD_TNW4_L_AT 88           // LANDED barrier in front of this MFMA; the next slab's half-0 reads follow it, one per MFMA
-#endif
-#ifndef OD_TNW4_X
-#define OD_TNW4_X 0        // timing experiments only (wrong results): 2 no loop fragment reads, 16 no fetch
 #endif
 __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const bf16_t* __restrict__ G, int ldg, const bf16_t* __restrict__ A, int lda,
                                                             float* __restrict__ dW, int lddw, float* __restrict__ dbias,
@@ -1203,7 +1126,6 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const bf16_t* __rest
     const bf16_t* opnd = (isa ? A : G) + (size_t)mb * ld + c0;
     const long avail = (long)(me - mb - 1) * ld + ((width - c0 + 7) & ~7);
     od_srd_t srd = od_make_srd(opnd, (unsigned)((avail > 0 ? avail : 0) * 2));
-    if (OD_TNW4_X & 16) od_srd_set_bytes(srd, 0u);
     unsigned voff8[8];                                                       // by piece & 7 (the swizzle key is row & 15 = (2 i + lane / 32) & 15)
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -1302,10 +1224,8 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_w4_kernel(const bf16_t* __rest
             const bool d = n >= 33 && n < 33 + 16 * OD_TNW4_DMA_EVERY && (n - 33) % OD_TNW4_DMA_EVERY == 0;         // 16 pieces at MFMAs 33, 36, ..., 78
             const int q = (n - 33) / OD_TNW4_DMA_EVERY;
             if (d) od_dma_set_dst(dst + (unsigned)q * 1024u);
-            if (!(OD_TNW4_X & 2)) {
-                if (n < 32) rd_one(1, n);
-                if (n >= OD_TNW4_L_AT && n < OD_TNW4_L_AT + 32) rd_one(0, n - OD_TNW4_L_AT);
-            }
+            if (n < 32) rd_one(1, n);
+            if (n >= OD_TNW4_L_AT && n < OD_TNW4_L_AT + 32) rd_one(0, n - OD_TNW4_L_AT);
             if (n >= 40 && n < 56) offs[n - 40] ^= 65536u;                     // the read addresses move to the other stage
             if (n == 56) { boff[0] ^= 65536u; boff[1] ^= 65536u; }
             mma_one(n >> 6, n & 63);
@@ -1376,28 +1296,22 @@ int launch_nt(const T* A, int lda, const T* W, int ldw, const float* bias, T* C,
 #define OD_GEMM_SMALL_TILES 512     // fewer 128-row tiles than 2 per CU: use 64-row tiles (the emulator build lowers it)
 #endif
     const bool half = ((M + 127) / 128) * tiles_n < OD_GEMM_SMALL_TILES;
-#ifndef OD_GEMM_QUARTER_TILES
-#define OD_GEMM_QUARTER_TILES 0      // bf16: 32-row tiles never paid (out 13.0 -> 12.2 us, proj_o 14.6 -> 15.5 us at M = 4460)
-#endif
 #ifndef OD_GEMM_QUARTER_TILES_F32
 #define OD_GEMM_QUARTER_TILES_F32 600   // fp32 products (fp32-as-3xbf16 measured +-0: left on 64-row tiles) (32-float k slabs: twice the iterations of bf16, one wave per SIMD at 64-row
                                         // tiles): 32-row tiles put two workgroups on a CU — out 74 -> 60 us, proj_o 100 -> 80 us at M = 4460
 #endif
-    const bool quarter = ((M + 63) / 64) * tiles_n < (std::is_same<T, float>::value ? OD_GEMM_QUARTER_TILES_F32 : OD_GEMM_QUARTER_TILES);
+    // 32-row tiles for plain fp32 only: for bf16 they never paid (out 13.0 -> 12.2 us, proj_o 14.6 -> 15.5 us at M = 4460)
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const bool quarter = f32 && ((M + 63) / 64) * tiles_n < OD_GEMM_QUARTER_TILES_F32;
     const int tiles_m = quarter ? (M + 31) / 32 : half ? (M + 63) / 64 : (M + 127) / 128;
     const int grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
     const bool dma = (K % (128 / (int)sizeof(T))) == 0;
     // q/k norm + RoPE in the large-M kernel's epilogue: bf16, head_dim 64 (a wave's 64 columns are one head), whole 256-column tiles
     const bool big_rope = epi == OD_EPI_QKROPE && std::is_same<T, bf16_t>::value && rp.hd == 64 && rp.n_rope % 64 == 0 && N % 64 == 0 &&
                           (!rp.qk_out || rp.ldqk % 8 == 0);
-    // Below OD_GEMM_BIG_MIN_M rows (the sampler: M = 4460) a product whose 256 x 256 tiles fill most of the chip in ONE round — qkv (N = 3072:
-    // 216 tiles) and proj_vg (N = 2816: 198) — still takes the 4-wave persistent kernel: its tile time beats the 128-row kernel's three rounds
-    // (round 6: profiles/r06b_ab_sampler_big_tiles.txt).  OD_NT_BIG_MIN_TILES: the fewest tiles for that (0 = never).
-    static const int big_min_tiles = od_env_int("OD_NT_BIG_MIN_TILES", OD_NT_BIG_MIN_TILES);
-    const int tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
-    const bool big_by_tiles = std::is_same<T, bf16_t>::value && big_min_tiles > 0 && M >= 1024 && tiles256 >= big_min_tiles && tiles256 <= od_num_cus() &&
-                              !accumulate && K % 128 == 0;
-    if ((epi != OD_EPI_QKROPE || big_rope) && dma && (M >= OD_GEMM_BIG_MIN_M || big_by_tiles) && N % 8 == 0 && ldc % 8 == 0 && N >= 256) {
+    // (Below OD_GEMM_BIG_MIN_M rows — the sampler: M = 4460 — the 4-wave persistent kernel on products whose 256 x 256 tiles fill the chip in
+    // one round measured slower than the 128-row kernel: profiles/r06a_ab_sampler_big_tiles.txt.)
+    if ((epi != OD_EPI_QKROPE || big_rope) && dma && M >= OD_GEMM_BIG_MIN_M && N % 8 == 0 && ldc % 8 == 0 && N >= 256) {
         const int tm2 = (M + 255) / 256, tn2 = (N + 255) / 256;
         const int grid2 = ((tm2 + 7) / 8) * 8 * tn2;
         // Wide outputs are written with non-temporal stores: the 128 KiB tile bursts of 256 CUs (32 MiB, the size of all L2s) otherwise
@@ -1405,10 +1319,7 @@ int launch_nt(const T* A, int lda, const T* W, int ldw, const float* bias, T* C,
         // (profiles/r02l_gemm_fetch_bound.txt): +7..12 % at N = 1024..2816, +2.5 % at 3072; at N = 512 (2 column tiles) it costs 3 %.
         const int nt_store = !accumulate && N >= OD_GEMM_NT_STORE_MIN_N;
         if constexpr (std::is_same<T, bf16_t>::value) {
-            static const int w4 = od_env_int("OD_NT_W4", 1);
-            static const int w4_min_k = od_env_int("OD_NT_W4_MIN_K", 0);
-            static const int w4_rope = od_env_int("OD_NT_W4_QKROPE", 1);      // (0: the 8-wave kernel's norm + RoPE epilogue; A/B)
-            if ((rp.f16 || (w4 && (epi != OD_EPI_QKROPE || w4_rope) && K >= w4_min_k)) && !accumulate && K % 128 == 0) {
+            if (!accumulate && K % 128 == 0) {
                 int pgrid = od_num_cus() & ~7;                 // persistent: one workgroup per CU, a multiple of 8 (block b runs on XCD b % 8)
                 pgrid = pgrid < 8 ? 8 : pgrid;
                 if (epi == OD_EPI_QKROPE)
@@ -1433,7 +1344,7 @@ int launch_nt(const T* A, int lda, const T* W, int ldw, const float* bias, T* C,
     }
     if (epi == OD_EPI_QKROPE && rp.qk_out) return OD_ERR_UNSUPPORTED;      // the split form exists in the large-M kernel only (callers check)
 #define NT_GO(EPI_, DMA_, WMT_) OD_LAUNCH_DYN((gemm_nt_kernel<T, EPI_, DMA_, WMT_>), dim3(grid), dim3(256), (gemm_nt_smem_bytes<T, DMA_, WMT_>()), st, A, lda, W, ldw, bias, C, ldc, M, N, K, accumulate, rp)
-#define NT_GO2(EPI_, DMA_) do { if (quarter) NT_GO(EPI_, DMA_, 1); else if (half) NT_GO(EPI_, DMA_, 2); else NT_GO(EPI_, DMA_, 4); } while (0)
+#define NT_GO2(EPI_, DMA_) do { if (quarter) NT_GO(EPI_, DMA_, f32 ? 1 : 2); else if (half) NT_GO(EPI_, DMA_, 2); else NT_GO(EPI_, DMA_, 4); } while (0)
     if (epi == OD_EPI_QKROPE) {
         if (dma) NT_GO2(OD_EPI_QKROPE, true); else NT_GO2(OD_EPI_QKROPE, false);
     } else if (epi == OD_EPI_SILU) {
@@ -1457,47 +1368,15 @@ int launch_tn(const T* G, int ldg, const T* A, int lda, float* dW, int lddw, flo
 #ifndef OD_TN_BLOCKS
 #define OD_TN_BLOCKS 256     // one workgroup per CU: M-splits = 256 / output tiles (fewest fp32 atomics, no second block wave)
 #endif
-#ifndef OD_TN_XCD_MIN_TILES
-#define OD_TN_XCD_MIN_TILES 16
-#endif
-            static const int xcd_min_tiles = od_env_int("OD_TN_XCD_MIN_TILES", OD_TN_XCD_MIN_TILES);
-            static const int eff_pct = od_env_int("OD_TN_EFF_PCT", 100);      // take the SMALLEST k whose fill efficiency reaches this
-            // packed order (round 3) below `xcd_min_tiles` output tiles; from there on the round-2 order (8 k splits, whole splits per XCD, several
-            // block rounds), which still wins on the 24-tile qkv shape (777 vs 750 TF/s).  OD_TN_PACK=0 / 2: never / always packed (A/B).
-            // Round 5: with the 4-wave kernel the packed order wins on every shape of the step — qkv (24 tiles) 803 against 811 us, the merged
-            // 22-tile proj_vg gradient 746 against 924 (the round-2 order takes 56 M-splits there: 80 M epilogue atomics) — and is the default.
-            static const int pack_mode = od_env_int("OD_TN_PACK", 2);
-            int xcd_order = tiles2 >= xcd_min_tiles;
-            const bool pack = pack_mode == 2 || (pack_mode == 1 && !xcd_order);
-            int sp, grid_tn;
-            if (pack) {
-                // fewest M-splits that fill the chip, whole splits side by side on an XCD (see the kernel): tiles2 x sp <= 256 workgroups
-                sp = OD_TN_BLOCKS / tiles2 > 0 ? OD_TN_BLOCKS / tiles2 : 1;
-            } else if (xcd_order) {
-                // M-splits = 8 k: each XCD (32 CUs, one workgroup each) holds k splits x tiles2 tiles; pick the k whose k * tiles2 fills
-                // whole waves of 32 workgroups best (qkv: 24 tiles -> k = 4 -> 96 = 3 x 32)
-                int best_k = 1; double best_eff = 0.0;
-                for (int kk = 1; kk <= 8; kk++) {
-                    const int bpx = kk * tiles2, waves = (bpx + 31) / 32;
-                    const double eff = (double)bpx / (waves * 32);
-                    if (eff > best_eff + 1e-9) { best_eff = eff; best_k = kk; }
-                    if (eff * 100.0 >= eff_pct - 1e-9) { best_k = kk; break; }
-                }
-                static const int force_k = od_env_int("OD_TN_KK", 0);                // A/B: M-splits per XCD given outright
-                if (force_k > 0) best_k = force_k;
-                sp = 8 * best_k;
-            } else {
-                sp = OD_TN_BLOCKS >= 512 ? (OD_TN_BLOCKS + tiles2 - 1) / tiles2 : (OD_TN_BLOCKS / tiles2 > 0 ? OD_TN_BLOCKS / tiles2 : 1);
-            }
+            // packed order (see the kernel).  It won on every shape of the step against the round-2 order (8 k M-splits, whole splits per
+            // XCD): qkv (24 tiles) 803 against 811 us, the merged 22-tile proj_vg gradient 746 against 924 (56 M-splits there: 80 M epilogue
+            // atomics).  Fewest M-splits that fill the chip, whole splits side by side on an XCD: tiles2 x sp <= 256 workgroups.
+            int sp = OD_TN_BLOCKS / tiles2 > 0 ? OD_TN_BLOCKS / tiles2 : 1;
             int mpb2 = (M + sp - 1) / sp;
             mpb2 = ((mpb2 + 63) / 64) * 64;
             sp = (M + mpb2 - 1) / mpb2;
-            if (pack) {
-                const int per_xcd = (tiles2 * sp + 7) / 8;
-                xcd_order = (per_xcd << 2) | 2;
-                grid_tn = per_xcd * 8;
-            } else
-                grid_tn = xcd_order ? ((sp + 7) / 8) * 8 * tiles2 : tiles2 * sp;
+            const int per_xcd = (tiles2 * sp + 7) / 8;
+            const int xcd_order = (per_xcd << 2) | 2, grid_tn = per_xcd * 8;
             OD_LAUNCH_DYN(gemm_tn_w4_kernel, dim3(grid_tn), dim3(256), (131072 + 1024), st, G, ldg, A, lda, dW, lddw, dbias, M, N, K, mpb2, xcd_order, od_det_active(), rm);
             OD_CHECK_LAUNCH();
             return 0;
@@ -1506,8 +1385,7 @@ int launch_tn(const T* G, int ldg, const T* A, int lda, float* dW, int lddw, flo
     const int tiles = ((N + BN - 1) / BN) * ((K + BM - 1) / BM);
     // ~2048 workgroups (8 per CU) — but every M-split costs N x K fp32 atomics, and with few output tiles that is what the launch waits for
     // (proj_cl's dW, 4 tiles: 512 splits = 33.5 M atomics ~ 0.1 ms of a 0.155 ms launch): large-M launches with <= 8 tiles aim for 512
-    static const int few_tile_wgs = od_env_int("OD_TN_SMALL_WGS", 512);
-    const int target_wgs = (tiles <= 8 && M >= OD_GEMM_BIG_MIN_M) ? few_tile_wgs : 2048;
+    const int target_wgs = (tiles <= 8 && M >= OD_GEMM_BIG_MIN_M) ? 512 : 2048;
     int splits = (target_wgs + tiles - 1) / tiles;
     int mpb = (M + splits - 1) / splits;
     mpb = ((mpb + BR - 1) / BR) * BR;

@@ -8,9 +8,6 @@
 
 namespace {
 
-#ifndef OD_QK_POS
-#define OD_QK_POS 1       // q/k norm + RoPE: the position-major kernel where its shape conditions hold (0 = always the generic kernel)
-#endif
 #ifndef OD_QK_BPW
 #define OD_QK_BPW 8       // batch rows a wave of the position-major kernel handles per position
 #endif
@@ -1031,7 +1028,7 @@ extern "C" int od_qk_norm_rope(int dtype, const void* qkv, int ldqkv, const floa
     if (ldqkv % 8 || ldo % 8) return OD_ERR_ALIGN;
     const long M = (long)B * L;
     const int lph = hd / 8;
-    if (OD_QK_POS && dtype != OD_F16 && (lph == 4 || lph == 8) && (H * lph) % 64 == 0 && ldqkv >= 2 * H * hd) {      // position-major kernel
+    if (dtype != OD_F16 && (lph == 4 || lph == 8) && (H * lph) % 64 == 0 && ldqkv >= 2 * H * hd) {      // position-major kernel
         const int nit = 2 * H * lph / 64;
         if (nit == 2 || nit == 4 || nit == 8) {
             int bpw, lpw; qk_pos_split(B, L, bpw, lpw);
@@ -1068,7 +1065,7 @@ extern "C" int od_qk_norm_rope_bwd(int dtype, const void* qkv, int ldqkv, const 
     if (ldqkv % 8 || lddqk % 8 || lddqkv % 8) return OD_ERR_ALIGN;
     const long M = (long)B * L;
     const int lph = hd / 8;
-    if (OD_QK_POS && (lph == 4 || lph == 8) && (H * lph) % 64 == 0) {      // position-major kernel
+    if ((lph == 4 || lph == 8) && (H * lph) % 64 == 0) {      // position-major kernel
         const int nit = 2 * H * lph / 64;
         if (nit == 2 || nit == 4 || nit == 8) {
             int bpw, lpw; qk_pos_split(B, L, bpw, lpw);

@@ -128,8 +128,7 @@ class DenoiserEngine:
         MFMAs per product; no-grad only): the weights are split into their bf16 (hi, lo) halves HERE, once per call, instead of in every
         fragment load of every GEMM of the 51 evaluations (ops.SplitWeight, OD_F32X3W) — wherever K is a multiple of 32."""
         dev = self.model.arena.data.device
-        import os
-        x3 = bool(x3 and dtype == torch.float32 and not train and os.environ.get("OD_X3_SPLIT", "1") != "0")      # (env: A/B only)
+        x3 = bool(x3 and dtype == torch.float32 and not train)
         key = (dtype, train, dev, x3)
         if self._packed_key != key:
             self._packed = {}

@@ -324,33 +324,7 @@ class DiffusionModel(nn.Module):
             eng.pred(xs, u, v)
             ops.sampler_step(xs, u, v, eta)
 
-        steps = range(num_steps)
-        if show_progress:
-            try:
-                import tqdm
-                steps = tqdm.trange(num_steps)
-            except ImportError:
-                pass
-        if self.use_graph and dev.type == "cuda" and num_steps > 1 and not eng._drop_active():     # (a training-mode Dropout1d draws a mask per step)
-            # the captured step only references plan-owned buffers (x, u, v, eta, workspace, packed weights), so one
-            # instantiated graph serves later calls — as long as those buffers are the SAME allocations: a forward or
-            # train step with another shape in between re-plans (new workspace / packed weights), which bumps
-            # `generation` and retires the graph even when the plan key comes back equal
-            from .graph import CapturedLoop
-            from . import det
-            key = (eng._plan_key, eng._packed_key, eng.generation, det.enabled())     # (a captured step carries the deterministic mode's launches)
-            if self._graph is None or self._graph[0] != key:
-                if self._graph is not None:
-                    self._graph[1].close()
-                self._graph = (key, CapturedLoop(step, dev))
-            loop = self._graph[1]
-            loop.begin()
-            for _ in steps:
-                loop.replay()
-            loop.end()
-        else:
-            for _ in steps:
-                step()
+        self._run_steps(step, num_steps, dev, show_progress)
         return xs.clone()
 
     @torch.no_grad()
@@ -411,9 +385,8 @@ class DiffusionModel(nn.Module):
         return [xs[offs[g]:offs[g + 1], :, :Ls[g]].clone() for g in range(G)]
 
     def _run_steps(self, step, num_steps: int, dev, show_progress: bool):
-        """The sampler loop of sample_many: hipGraph-captured under sample()'s rules (one slot, keyed by the plan — whose key carries the
-        varlen flag — the packed weights, their generation and the deterministic mode); the lengths are device data, not part of the key.
-        (sample() keeps its own copy of this loop, unchanged.)"""
+        """The sampler loop of sample and sample_many, hipGraph-captured in one slot keyed by the plan (whose key carries the varlen flag),
+        the packed weights, their generation and the deterministic mode; sample_many's lengths are device data, not part of the key."""
         eng = self.engine
         steps = range(num_steps)
         if show_progress:
@@ -422,10 +395,14 @@ class DiffusionModel(nn.Module):
                 steps = tqdm.trange(num_steps)
             except ImportError:
                 pass
-        if self.use_graph and dev.type == "cuda" and num_steps > 1 and not eng._drop_active():
+        if self.use_graph and dev.type == "cuda" and num_steps > 1 and not eng._drop_active():     # (a training-mode Dropout1d draws a mask per step)
+            # the captured step only references plan-owned buffers (x, u, v, eta, workspace, packed weights), so one
+            # instantiated graph serves later calls — as long as those buffers are the SAME allocations: a forward or
+            # train step with another shape in between re-plans (new workspace / packed weights), which bumps
+            # `generation` and retires the graph even when the plan key comes back equal
             from .graph import CapturedLoop
             from . import det
-            key = (eng._plan_key, eng._packed_key, eng.generation, det.enabled())
+            key = (eng._plan_key, eng._packed_key, eng.generation, det.enabled())     # (a captured step carries the deterministic mode's launches)
             if self._graph is None or self._graph[0] != key:
                 if self._graph is not None:
                     self._graph[1].close()

@@ -16,7 +16,7 @@ def setup(dev, B=32, L=8192, H=16, hd=64):
     o = torch.zeros(M, dh, dtype=bf, device=dev)
     lse, delta = torch.zeros(B, H, L, device=dev), torch.zeros(B, H, L, device=dev)
     dqk, dqkv = torch.zeros_like(qk), torch.zeros_like(qkv)
-    aux = ops.AttnAux() if os.environ.get("OD_BWD_2STREAM", "1") != "0" and hasattr(ops, "AttnAux") else None
+    aux = ops.AttnAux() if hasattr(ops, "AttnAux") else None
     fwd = lambda: ops.flash_attn_fwd(qk[:, :dh], qk[:, dh:], qkv[:, 2 * dh:], o, lse, B, H, L, hd, sc, q_prescaled=True)
     bwd = lambda: ops.flash_attn_bwd(qk[:, :dh], qk[:, dh:], qkv[:, 2 * dh:], o, do, lse, delta, dqk[:, :dh], dqk[:, dh:], dqkv[:, 2 * dh:],
                                      B, H, L, hd, sc, q_prescaled=True, aux=aux)

@@ -1,5 +1,4 @@
-"""One NT GEMM shape, a few launches, for counter runs: python3 tools/mb_nt_one.py N K [vendor]
-(the 4-wave kernel is the default; OD_NT_W4=0 in the environment selects the 8-wave kernel)."""
+"""One NT GEMM shape, a few launches, for counter runs: python3 tools/mb_nt_one.py N K [vendor]"""
 import os, sys
 import torch
 sys.path.insert(0, os.getcwd())

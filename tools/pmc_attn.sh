@@ -3,7 +3,6 @@
 out=$1; which=$2; lib=$3; mkdir -p $out
 export TMPDIR=/tmp
 [ -n "$lib" ] && export OSU_DREAMER_HIP_LIB=$PWD/$lib
-export OD_BWD_2STREAM=0
 : > $out/pmc_attn_$which.txt
 for set in "GRBM_GUI_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU" "SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_BF16" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_SALU"; do
   rm -rf $out/p

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Counters of one long-K NT GEMM shape under the 8-wave kernel, the 4-wave kernel and the vendor library.
+# Counters of one long-K NT GEMM shape under the 4-wave kernel and the vendor library.
 #   tools/pmc_nt.sh <outdir> [N K] [sets: "issue" | "mem"]  ->  <outdir>/pmc_nt.txt
 out=${1:-gpurun_out/pmc_nt}; N=${2:-512}; K=${3:-3072}; which=${4:-issue}; mkdir -p $out
 export TMPDIR=/tmp
@@ -9,12 +9,10 @@ if [ $which = issue ]; then
 else
   sets=("FETCH_SIZE WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_REQ_sum TCC_EA0_RDREQ_sum" "TCP_TCC_READ_REQ_sum GRBM_GUI_ACTIVE")
 fi
-for var in own8 own4 vendor; do
+for var in own vendor; do
   for set in "${sets[@]}"; do
     rm -rf $out/p
-    export OD_NT_W4=0; arg=""            # the 4-wave kernel has been the default since round 3: the 8-wave one has to be asked for
-    [ $var = own4 ] && export OD_NT_W4=1
-    [ $var = vendor ] && arg=vendor
+    arg=""; [ $var = vendor ] && arg=vendor
     timeout 300 rocprofv3 --pmc $set -d $out/p -o res -- python3 tools/mb_nt_one.py $N $K $arg > $out/p.log 2>&1
     flt=gemm_nt; [ $var = vendor ] && flt=Cijk
     echo "== $var [$set]" >> $out/pmc_nt.txt

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Counters + timing of the qkv projection's norm + RoPE epilogue kernel (gemm_nt_w4_kernel<2>) under the variant libraries in gpurun_variants/
-# (built by tools/build_variant.sh <name> "-DOD_W4Q_X=..." gemm) against the in-tree build and the plain GEMM of the same shape.
+# (built by tools/build_variant.sh <name> "-D..." gemm) against the in-tree build and the plain GEMM of the same shape.
 #   tools/pmc_qkrope.sh <outdir> [variant names...]   ->  <outdir>/pmc_qkrope.txt
 out=${1:-gpurun_out/pmc_qkrope}; shift; mkdir -p $out
 export TMPDIR=/tmp
