@@ -353,6 +353,36 @@ int od_chart_head(int dtype, const void* x, int ldx, const float* W, const float
  * replaces: AttnPool.forward, latent/model.py:33-36 (the two 1x1 convs before it are od_gemm_nt). */
 int od_attn_pool(int dtype, const void* scores, int lds, const void* values, int ldv, float* out, int B, int L, int Hh, int hd,
                  void* stream);
+/* ---- varlen forms of the latent kernels: G songs / maps stacked in the padded [B*L][C] layout; lens (device int32 [B]) = valid
+ *      frames of sequence b at the level the call reads.  Taps and frames at or past lens[b] read as zero (selected, so padding may
+ *      hold NaN) and frames there that the call writes come back as exact zeros.  Valid frames are bit for bit the plain call on
+ *      that sequence alone. ---- */
+/* od_spec_features_conv per sequence.  replaces: spec_features.py:17-26 on spectrograms zero-padded to a common length. */
+int od_spec_features_conv_varlen(int dtype, const float* audio, const float* w1, const float* b1, const float* g1, const float* w2,
+                                 const float* b2, const float* g2, void* out, int ldo, const int* lens, int B, int F, int L, float eps,
+                                 void* stream);
+/* od_rmsnorm_affine_film with frames >= lens[b] written as 0.  replaces: unet.py:53 (out_norm), per sequence. */
+int od_rmsnorm_affine_film_varlen(int dtype, const void* x, int ldx, const float* gamma, const float* ssg, void* y, int ldy,
+                                  const int* lens, int B, int L, int C, float eps, int act, void* stream);
+/* od_unet_mixer where row b reads its skip from row prow[b] of p (device int32 [B]): several decoder rows per song share the song's
+ * skip.  replaces: unet.py:117-126 (mixer), per song. */
+int od_unet_mixer_varlen(int dtype, const void* x, int ldx, const void* p, int ldp, const int* prow, const void* gx, int ldg,
+                         const float* gamma, void* xo, int ldxo, int B, int L, int C, float eps, void* stream);
+/* od_unet_down with lens at the INPUT level (Lo*stride frames of stride); outputs lo >= lens[b]/stride are 0.
+ * replaces: unet.py:58-63, per sequence. */
+int od_unet_down_varlen(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, const int* lens,
+                        int B, int Lo, int C, int stride, void* stream);
+/* od_unet_up with lens at the INPUT level (Li frames of stride); outputs l >= lens[b]*stride are 0.
+ * replaces: unet.py:80-85, per sequence. */
+int od_unet_up_varlen(int dtype, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, const int* lens,
+                      int B, int Li, int C, int stride, void* stream);
+/* od_chart_head with out[b][n][l >= lens[b]] = 0.  replaces: latent/model.py:114,127-131; :65-68, per sequence. */
+int od_chart_head_varlen(int dtype, const void* x, int ldx, const float* W, const float* bias, float* out, const int* lens, int B,
+                         int L, int C, int N, int n_sigmoid, int rms, float eps, void* stream);
+/* od_attn_pool over frames l < lens[b] of each sequence; lens[b] >= 1 is expected (a sequence with no frame pools to 0 rather than
+ * to the 0/0 of a softmax over nothing).  replaces: AttnPool.forward, latent/model.py:33-36, per sequence. */
+int od_attn_pool_varlen(int dtype, const void* scores, int lds, const void* values, int ldv, float* out, const int* lens, int B,
+                        int L, int Hh, int hd, void* stream);
 
 /* ---- data-parallel exchange: RCCL over xGMI (no counterpart in the reference, which is
  *      single-device, models/diffusion/model.yml:11 `devices: 1`) ------------------------------------------------- */

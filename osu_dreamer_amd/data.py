@@ -20,6 +20,39 @@ from torch.utils.data import DataLoader, IterableDataset
 NUM_LABELS = 5
 
 
+def read_spec(path) -> np.ndarray:
+    """A pre-processed `spec.npy` -> float64 (F, L): the stored unsigned integers scaled to [0, 1] by their dtype's maximum
+    (data/load_audio.py:58-59)."""
+    a = np.load(path)
+    return a.astype(np.float64) / np.iinfo(a.dtype).max
+
+
+def read_beatmap(path) -> Tuple[np.ndarray, np.ndarray]:
+    """A pre-processed `<map>.map.npy` (an npz: hit, xy, xy_min, xy_rng, labels) -> (chart float64 (9, L), labels): the hit rows scaled
+    to [0, 1], then the cursor rows mapped back to xy_min + [0, 1] * xy_rng, each scale taken from the array's integer dtype
+    (data/beatmap/encode.py:81-87)."""
+    with np.load(path) as d:
+        hit, xy, xy_min, xy_rng, labels = d["hit"], d["xy"], d["xy_min"], d["xy_rng"], d["labels"]
+    chart = np.concatenate([hit.astype(np.float64) / np.iinfo(hit.dtype).max,
+                            xy.astype(np.float64) / np.iinfo(xy.dtype).max * xy_rng + xy_min])
+    return chart, labels
+
+
+def spec_length(path) -> int:
+    """Frames of a `spec.npy`, from its header (the array is not read)."""
+    return int(np.load(path, mmap_mode="r").shape[-1])
+
+
+def beatmap_length(path) -> int:
+    """Frames of a `<map>.map.npy`, from the header of its `hit` member (the arrays are not read)."""
+    import zipfile
+    with zipfile.ZipFile(path) as z, z.open("hit.npy") as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        shape, _, _ = read(f)
+    return int(shape[-1])
+
+
 class LatentBatch(NamedTuple):
     h: torch.Tensor        # (A, l) audio features at latent rate
     z: torch.Tensor        # (E, l) chart latent

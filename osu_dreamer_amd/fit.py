@@ -285,11 +285,15 @@ def main(argv=None):
     f = sub.add_parser("fit-denoiser", help="begin a training run for the diffusion model")
     f.add_argument("-c", "--config", default=DEFAULT_CONFIG)
     f.add_argument("--ckpt-path", default=None)
+    from . import encode_latents as encode_cmd
     from . import predict as predict_cmd
+    encode_cmd.add_parser(sub)
     predict_cmd.add_parser(sub)
     a = ap.parse_args(argv)
     if a.cmd == "predict":
         return predict_cmd.run(a)
+    if a.cmd == "encode-latents":
+        return encode_cmd.run(a)
     if a.cmd == "fit-denoiser":
         with open(a.config) as fh:
             devices = launch.parse_devices((yaml.safe_load(fh).get("trainer") or {}).get("devices", 1))

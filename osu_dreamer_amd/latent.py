@@ -9,6 +9,13 @@ reference checkpoint / inference artifact loads with `strict=True`), and the cal
     chart, labels = model.decode(z, s, skips=skips) # or audio=...;   also decode_logits(z, s, ...)
     z, s = model.encode_chart(chart)                # (B,9,L) -> (B,emb_dim,L/chunk), (B,style_dim)
 
+Each call also takes sequences of different lengths at once (`lengths=`, no-grad, the varlen kernels): they are stacked zero-padded to
+a common length, each keeps to its own frames, and every frame past a sequence's length comes back as exactly 0:
+
+    skips, h = model.audio_encoder(audio, lengths=Ls)                   # audio (G,72,Lpad), Ls[g] a multiple of chunk_size
+    chart, labels = model.decode(z, s, skips=skips, lengths=Ls, offs=offs)  # z (B,E,Lpad/chunk): rows offs[g]:offs[g+1] are song g's
+    z, s = model.encode_chart(chart, lengths=Ls)                        # chart (B,9,Lpad), one length per map
+
 Activations are frame-major [B*L][h_dim] on the device; the tensors handed back are (B, C, L)-shaped *views* of
 those buffers (no transposing copy), and `decode` takes them back without one.  `encode_chart(chart) -> (z, s)`
 (chart encoder, style head, temporal head: the dataset-encoding direction of scripts/encode_latents.py) runs on
@@ -19,7 +26,7 @@ from __future__ import annotations
 import math
 import weakref
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -60,8 +67,8 @@ class _Node(nn.Module):
 class _AudioEncoder(_Node):
     """`model.audio_encoder(audio)` — holds the reference's `audio_encoder.{0,1}.*` parameters."""
 
-    def forward(self, audio: torch.Tensor):
-        return self._owner()._audio_encoder(audio)
+    def forward(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None):
+        return self._owner()._audio_encoder(audio, lengths)
 
 
 def _shapes(emb_dim: int, style_dim: int, n_downs: int, stride: int, a: LatentModelArgs):
@@ -249,10 +256,33 @@ class LatentModel(nn.Module):
             ws = self._ws[key] = Workspace(dev)
         return ws
 
+    def _check_lengths(self, lengths: Sequence[int], n: int, L: int, what: str) -> List[int]:
+        lengths = [int(x) for x in lengths]
+        if len(lengths) != n:
+            raise ValueError(f"{what}: expected {n} lengths, got {len(lengths)}")
+        for x in lengths:
+            if x < self.chunk_size or x > L or x % self.chunk_size:
+                raise ValueError(f"{what}: length {x} is not a multiple of chunk_size {self.chunk_size} in [{self.chunk_size}, {L}]")
+        return lengths
+
+    @staticmethod
+    def _dev_i32(rows: List[List[int]], dev) -> torch.Tensor:
+        """Host ints -> device int32, without waiting for the stream (pinned source, asynchronous copy)."""
+        t = torch.tensor(rows, dtype=torch.int32)
+        if dev.type != "cuda":
+            return t.to(dev)
+        return t.pin_memory().to(dev, non_blocking=True)
+
+    def _level_lens(self, lengths: List[int], dev) -> torch.Tensor:
+        """Frame-0 lengths (multiples of chunk_size) of B rows -> (n_downs + 1, B) device int32: row i = the lengths at level i."""
+        return self._dev_i32([[x // self.stride ** i for x in lengths] for i in range(self.n_downs + 1)], dev)
+
     # ------------------------------------------------------------------ unet.py:21-53 (layer)
     def _layer(self, ws: Workspace, tag: str, p: str, x: torch.Tensor, cond: Optional[torch.Tensor], B: int, L: int,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B*L][D] is updated in place by the blocks; returns out_norm(x) in `out` (or a workspace buffer)."""
+               out: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B*L][D] is updated in place by the blocks; returns out_norm(x) in `out` (or a workspace buffer).
+        `lens` (device int32 [B]): row b is valid for frames < lens[b]; the depthwise convs stop there and the returned out_norm is 0 past it
+        (everything else in a block is row-wise, so padded frames only ever affect themselves)."""
         M, D, dt, x3 = B * L, self.a_dim, x.dtype, self._x3()
         h = ws.get(tag + ".h", (M, D), dt)
         hd = ws.get(tag + ".hd", (M, D), dt)
@@ -268,32 +298,45 @@ class LatentModel(nn.Module):
                 ops.linear_small(cond, self.P(f"{p}films.{i}.weight"), self.P(f"{p}films.{i}.bias"), ssg)
             b = f"{p}blocks.{i}.0."
             ops.rmsnorm_affine_film(x, self.P(f"{p}norms.{i}.gamma"), ssg, h, B, L)
-            ops.dwconv(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, B, L, k)
+            if lens is None:
+                ops.dwconv(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, B, L, k)
+            else:
+                ops.dwconv_varlen(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, lens, B, L, k)
             ops.gemm_nt(hd, self._packed[b + "proj_vg.1"], self._packed[b + "proj_vg.1.b"], vg, x3=x3)
             ops.swiglu_rmsnorm(vg, hh, inv, self.hf, self.hp)
             ops.gemm_nt(hh, self._packed[b + "proj_o"], self.P(b + "proj_o.bias"), fo, x3=x3)
             ops.rmsnorm_affine_gate_residual(x, fo, self.P(f"{p}blocks.{i}.1.gamma"), ssg, x, B, L)
         if out is None:
             out = ws.get(tag + ".out", (M, D), dt)
-        ops.rmsnorm_affine_film(x, self.P(p + "out_norm.gamma"), None, out, B, L)
+        if lens is None:
+            ops.rmsnorm_affine_film(x, self.P(p + "out_norm.gamma"), None, out, B, L)
+        else:
+            ops.rmsnorm_affine_film_varlen(x, self.P(p + "out_norm.gamma"), None, out, lens, B, L)
         return out
 
     # ------------------------------------------------------------------ latent/model.py:54 (audio_encoder)
     @torch.no_grad()
-    def _audio_encoder(self, audio: torch.Tensor):
+    def _audio_encoder(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None):
+        """`lengths` (one per row, multiples of chunk_size): row g of audio holds a song of lengths[g] frames, zero-padded to L; the skips
+        and h are then 0 past each song's length at every level."""
         audio = audio.detach().to(torch.float32).contiguous()
         Ba, F, L = audio.shape
         if F != A_DIM:
             raise ValueError(f"audio must have {A_DIM} spectrogram bins, got {F}")
         if L % self.chunk_size:
             raise ValueError(f"audio length {L} is not a multiple of chunk_size {self.chunk_size} (pad_to_multiple first)")
+        lv = None if lengths is None else self._level_lens(self._check_lengths(lengths, Ba, L, "audio_encoder"), audio.device)
         dt, D, x3 = self._dtype(), self.a_dim, self._x3()
         self._pack(dt)
         ws = self._workspace("enc", Ba, L, dt)
         p = "audio_encoder.0.net."
         f96 = ws.get("f96", (Ba * L, 32 * (A_DIM // 24)), dt)
-        ops.spec_features_conv(audio, self.P(p + "1.weight"), self.P(p + "1.bias"), self.P(p + "2.gamma"),
-                               self.P(p + "4.weight"), self.P(p + "4.bias"), self.P(p + "5.gamma"), f96)
+        spec_w = (self.P(p + "1.weight"), self.P(p + "1.bias"), self.P(p + "2.gamma"), self.P(p + "4.weight"), self.P(p + "4.bias"),
+                  self.P(p + "5.gamma"))
+        if lv is None:
+            ops.spec_features_conv(audio, *spec_w, f96)
+        else:
+            ops.spec_features_conv_varlen(audio, *spec_w, f96, lv[0])
         pre = ws.get("pre", (Ba * L, D), dt)
         ops.gemm_nt(f96, self._packed["audio_encoder.0.net.8"], self.P(p + "8.bias"), pre, x3=x3)
         x = ws.get("x0", (Ba * L, D), dt)
@@ -302,13 +345,16 @@ class LatentModel(nn.Module):
         for i in range(self.n_downs):
             # the skip outlives this call: it gets its own storage, not a workspace slot
             skip = torch.empty(Ba * Li, D, dtype=dt, device=audio.device)
-            self._layer(ws, f"l{i}", f"audio_encoder.1.layers.{i}.", x, None, Ba, Li, out=skip)
+            self._layer(ws, f"l{i}", f"audio_encoder.1.layers.{i}.", x, None, Ba, Li, out=skip, lens=None if lv is None else lv[i])
             skips.append(skip.view(Ba, Li, D).permute(0, 2, 1))
             Lo = Li // self.stride
             x = (torch.empty(Ba * Lo, D, dtype=dt, device=audio.device) if i == self.n_downs - 1
                  else ws.get(f"x{i + 1}", (Ba * Lo, D), dt))
-            ops.unet_down(skip, self.P(f"audio_encoder.1.downs.{i}.0.weight"), self.P(f"audio_encoder.1.downs.{i}.0.bias"),
-                          x, Ba, Lo, self.stride)
+            dw = (self.P(f"audio_encoder.1.downs.{i}.0.weight"), self.P(f"audio_encoder.1.downs.{i}.0.bias"))
+            if lv is None:
+                ops.unet_down(skip, *dw, x, Ba, Lo, self.stride)
+            else:
+                ops.unet_down_varlen(skip, *dw, x, lv[i], Ba, Lo, self.stride)
             Li = Lo
         return skips, x.view(Ba, Li, D).permute(0, 2, 1)
 
@@ -324,17 +370,30 @@ class LatentModel(nn.Module):
 
     # ------------------------------------------------------------------ latent/model.py:103-114
     @torch.no_grad()
-    def _decode(self, z, s, audio, skips, n_sigmoid: int):
+    def _decode(self, z, s, audio, skips, n_sigmoid: int, lengths=None, offs=None):
+        if lengths is None and offs is not None:
+            raise ValueError("decode: `offs` goes with `lengths`")
         if skips is None:
             if audio is None:
                 raise ValueError("decode needs `audio` or `skips`")
-            skips, _ = self._audio_encoder(audio)
+            skips, _ = self._audio_encoder(audio, lengths)
         z = z.detach().to(torch.float32).contiguous()
         s = s.detach().to(torch.float32).contiguous()
         B, E, l = z.shape
         dt, D, x3 = self._dtype(), self.a_dim, self._x3()
         self._pack(dt)
-        ws = self._workspace("dec", B, l, dt)
+        lv = prow = None
+        if lengths is not None:
+            # varlen: song g = rows offs[g]:offs[g+1] of z / s, skips[i] row g; lengths[g] in chart frames
+            G = len(lengths)
+            offs = list(range(G + 1)) if offs is None else [int(o) for o in offs]
+            if len(offs) != G + 1 or offs[0] != 0 or offs[-1] != B or any(offs[g + 1] <= offs[g] for g in range(G)):
+                raise ValueError(f"decode: offs must rise from 0 to B = {B} in G + 1 = {G + 1} steps, got {offs}")
+            lengths = self._check_lengths(lengths, G, l * self.chunk_size, "decode")
+            rows = [g for g in range(G) for _ in range(offs[g + 1] - offs[g])]
+            lv = self._level_lens([lengths[g] for g in rows], z.device)
+            prow = self._dev_i32(rows, z.device)
+        ws = self._workspace("dec" if lv is None else f"dec.vl{len(lengths)}", B, l, dt)
         skips = list(skips)
         if len(skips) != self.n_downs:
             raise ValueError(f"expected {self.n_downs} skips, got {len(skips)}")
@@ -343,11 +402,19 @@ class LatentModel(nn.Module):
         Li = l
         for i in range(self.n_downs):
             Lu = Li * self.stride
+            lvl = self.n_downs - i                                # level of x; xu is at level lvl - 1
             xu = ws.get(f"xu{i}", (B * Lu, D), dt)
-            ops.unet_up(x, self.P(f"decoder.ups.{i}.1.weight"), self.P(f"decoder.ups.{i}.1.bias"), xu, B, Li, self.stride)
+            uw = (self.P(f"decoder.ups.{i}.1.weight"), self.P(f"decoder.ups.{i}.1.bias"))
+            if lv is None:
+                ops.unet_up(x, *uw, xu, B, Li, self.stride)
+            else:
+                ops.unet_up_varlen(x, *uw, xu, lv[lvl], B, Li, self.stride)
             sk = skips.pop()
             Bs = sk.shape[0]
-            if sk.shape[1] != D or sk.shape[2] != Lu or Bs not in (1, B):
+            if lv is not None:
+                if sk.shape[1] != D or sk.shape[2] != Lu or Bs != len(lengths):
+                    raise ValueError(f"skip {tuple(sk.shape)} does not match (G = {len(lengths)}, {D}, {Lu})")
+            elif sk.shape[1] != D or sk.shape[2] != Lu or Bs not in (1, B):
                 raise ValueError(f"skip {tuple(sk.shape)} does not match ({B}|1, {D}, {Lu})")
             skf = self._frames(sk, dt)
             m = f"decoder.mixers.{i}."
@@ -355,15 +422,22 @@ class LatentModel(nn.Module):
             ops.gemm_nt(skf, self._packed[m + "proj.0"], self.P(m + "proj.0.bias"), pr, x3=x3)
             gx = ws.get(f"gx{i}", (B * Lu, D), dt)
             ops.gemm_nt(xu, self._packed[m + "gate"], self.P(m + "gate.bias"), gx, x3=x3)
-            ops.unet_mixer(xu, pr, Bs == 1 and B > 1, gx, self.P(m + "proj.1.gamma"), xu, B, Lu)
-            x = self._layer(ws, f"l{i}", f"decoder.layers.{i}.", xu, s, B, Lu)
+            if lv is None:
+                ops.unet_mixer(xu, pr, Bs == 1 and B > 1, gx, self.P(m + "proj.1.gamma"), xu, B, Lu)
+            else:
+                ops.unet_mixer_varlen(xu, pr, prow, gx, self.P(m + "proj.1.gamma"), xu, B, Lu)
+            x = self._layer(ws, f"l{i}", f"decoder.layers.{i}.", xu, s, B, Lu, lens=None if lv is None else lv[lvl - 1])
             Li = Lu
         out = torch.empty(B, X_DIM, Li, dtype=torch.float32, device=z.device)
-        ops.chart_head(x, self.P("proj_out.weight").view(X_DIM, D), self.P("proj_out.bias"), out, B, Li, n_sigmoid)
+        hw = (self.P("proj_out.weight").view(X_DIM, D), self.P("proj_out.bias"))
+        if lv is None:
+            ops.chart_head(x, *hw, out, B, Li, n_sigmoid)
+        else:
+            ops.chart_head_varlen(x, *hw, out, lv[0], B, Li, n_sigmoid)
         return out, s
 
-    def decode_logits(self, z, s, *, audio=None, skips=None) -> torch.Tensor:
-        return self._decode(z, s, audio, skips, n_sigmoid=0)[0]
+    def decode_logits(self, z, s, *, audio=None, skips=None, lengths=None, offs=None) -> torch.Tensor:
+        return self._decode(z, s, audio, skips, n_sigmoid=0, lengths=lengths, offs=offs)[0]
 
     def _label_predictor(self, s: torch.Tensor) -> torch.Tensor:            # latent/model.py:72-76
         B = s.shape[0]
@@ -374,10 +448,11 @@ class LatentModel(nn.Module):
         return out
 
     @torch.no_grad()
-    def decode(self, z, s, *, audio=None, skips=None):
+    def decode(self, z, s, *, audio=None, skips=None, lengths=None, offs=None):
         """(chart, labels): sigmoid on the hit signals, cursor signals raw, labels clamped to [0, 10]
-        (latent/model.py:116-134)."""
-        chart, s32 = self._decode(z, s, audio, skips, n_sigmoid=N_HIT)
+        (latent/model.py:116-134).  Varlen: `lengths` (G songs, chart frames, multiples of chunk_size), `offs` (G + 1 row offsets of
+        z / s, default one row per song) and skips / audio with one row per song; the chart is 0 past each song's length."""
+        chart, s32 = self._decode(z, s, audio, skips, n_sigmoid=N_HIT, lengths=lengths, offs=offs)
         return chart, self._label_predictor(s32).clamp_(0, 10)
 
     @torch.no_grad()
@@ -386,15 +461,18 @@ class LatentModel(nn.Module):
 
     # ------------------------------------------------------------------ latent/model.py:93-101 (encode_chart)
     @torch.no_grad()
-    def encode_chart(self, chart: torch.Tensor):
+    def encode_chart(self, chart: torch.Tensor, lengths: Optional[Sequence[int]] = None):
         """chart (B, 9, L) -> z (B, emb_dim, L / chunk_size), s (B, style_dim): the dataset-encoding direction
-        (scripts/encode_latents.py): chart encoder, style head (layer + AttnPool + rms_norm), temporal layer / head."""
+        (scripts/encode_latents.py): chart encoder, style head (layer + AttnPool + rms_norm), temporal layer / head.
+        `lengths` (one per map, multiples of chunk_size): map b holds lengths[b] frames; z is 0 past lengths[b] / chunk_size and s pools
+        over the map's own frames."""
         chart = chart.detach().to(torch.float32).contiguous()
         B, X, L = chart.shape
         if X != X_DIM:
             raise ValueError(f"chart must have {X_DIM} signals, got {X}")
         if L % self.chunk_size:
             raise ValueError(f"chart length {L} is not a multiple of chunk_size {self.chunk_size} (pad_to_multiple first)")
+        lv = None if lengths is None else self._level_lens(self._check_lengths(lengths, B, L, "encode_chart"), chart.device)
         dt, D, x3 = self._dtype(), self.a_dim, self._x3()
         self._pack(dt)
         ws = self._workspace("chart", B, L, dt)
@@ -404,31 +482,41 @@ class LatentModel(nn.Module):
         ops.gemm_nt(cf, self._packed["chart_encoder.0"], self.P("chart_encoder.0.bias"), x, x3=x3)
         Li = L
         for i in range(self.n_downs):
-            y = self._layer(ws, f"l{i}", f"chart_encoder.1.layers.{i}.", x, None, B, Li)
+            y = self._layer(ws, f"l{i}", f"chart_encoder.1.layers.{i}.", x, None, B, Li, lens=None if lv is None else lv[i])
             Lo = Li // self.stride
             x = ws.get(f"x{i + 1}", (B * Lo, D), dt)
-            ops.unet_down(y, self.P(f"chart_encoder.1.downs.{i}.0.weight"), self.P(f"chart_encoder.1.downs.{i}.0.bias"),
-                          x, B, Lo, self.stride)
+            dw = (self.P(f"chart_encoder.1.downs.{i}.0.weight"), self.P(f"chart_encoder.1.downs.{i}.0.bias"))
+            if lv is None:
+                ops.unet_down(y, *dw, x, B, Lo, self.stride)
+            else:
+                ops.unet_down_varlen(y, *dw, x, lv[i], B, Lo, self.stride)
             Li = Lo
+        ll = None if lv is None else lv[self.n_downs]
         h = x                                                 # [B*l][D]; both heads below read it
         # style head: layer -> AttnPool -> rms_norm (no gain)
         hs = ws.get("hs", (B * Li, D), dt)
         hs.copy_(h)                                           # _layer updates its input in place
-        y = self._layer(ws, "sh", "style_head.0.", hs, None, B, Li)
+        y = self._layer(ws, "sh", "style_head.0.", hs, None, B, Li, lens=ll)
         heads, hd = self.args.style_heads, self.args.style_head_dim
         sc = ws.get("sc", (B * Li, heads), dt)
         va = ws.get("va", (B * Li, heads * hd), dt)
         ops.gemm_nt(y, self._packed["style_head.1.scores"], self.P("style_head.1.scores.bias"), sc, x3=x3)
         ops.gemm_nt(y, self._packed["style_head.1.values"], self.P("style_head.1.values.bias"), va, x3=x3)
         pooled = ws.get("pooled", (B, heads * hd), torch.float32)
-        ops.attn_pool(sc, va, pooled, B, Li, heads, hd)
+        if ll is None:
+            ops.attn_pool(sc, va, pooled, B, Li, heads, hd)
+        else:
+            ops.attn_pool_varlen(sc, va, pooled, ll, B, Li, heads, hd)
         s_pre = ws.get("s_pre", (B, self.style_dim), torch.float32)
         ops.linear_small(pooled, self.P("style_head.1.proj_out.weight"), self.P("style_head.1.proj_out.bias"), s_pre)
         s = torch.empty(B, self.style_dim, dtype=torch.float32, device=chart.device)
         ops.rmsnorm_rows(s_pre, None, s, 1e-6)
         # temporal layer (FiLM from s) -> Conv1d(D -> emb_dim) -> rms_norm over the emb_dim channels
-        y = self._layer(ws, "tl", "temporal_layer.", h, s, B, Li)
+        y = self._layer(ws, "tl", "temporal_layer.", h, s, B, Li, lens=ll)
         z = torch.empty(B, self.emb_dim, Li, dtype=torch.float32, device=chart.device)
-        ops.chart_head(y, self.P("temporal_head.0.weight").view(self.emb_dim, D), self.P("temporal_head.0.bias"), z, B, Li, 0,
-                       rms=True)
+        tw = (self.P("temporal_head.0.weight").view(self.emb_dim, D), self.P("temporal_head.0.bias"))
+        if ll is None:
+            ops.chart_head(y, *tw, z, B, Li, 0, rms=True)
+        else:
+            ops.chart_head_varlen(y, *tw, z, ll, B, Li, 0, rms=True)
         return z, s

@@ -92,24 +92,48 @@ class LDM(nn.Module):
                     s_init: Optional[Sequence[torch.Tensor]] = None, x_init: Optional[Sequence[torch.Tensor]] = None
                     ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """`sample` for G songs: audios[g] (72, L_g), labels[g] (B_g, 5) -> one (chart (B_g, 9, L_g), labels (B_g, 5)) pair per song.
-        The audio encoder, the style sampler and the decoder run per song exactly as in `sample`; the denoiser sampler runs once for all
-        songs (DiffusionModel.sample_many).  `s_init[g]` / `x_init[g]` pin song g's starting noise, as in `sample`."""
+        The audio encoder, the style sampler and the denoiser sampler each run once for all songs, stacked and zero-padded to a common
+        length, every song keeping to its own frames (the varlen kernels), with no host round trip between the stages.  The decoder runs
+        once for all songs in bf16 and once per song in fp32 (`_decode_songs`).  `s_init[g]` / `x_init[g]` pin song g's starting noise, as in `sample`; without them the noise is
+        drawn in the order G `sample` calls draw it (style noise per song, then latent noise per song)."""
         G = len(audios)
         if G == 0 or len(labels) != G or (s_init is not None and len(s_init) != G) or (x_init is not None and len(x_init) != G):
             raise ValueError("sample_many needs one audio and one label batch per song (and one s_init / x_init per song when given)")
-        enc = []
         for g, audio in enumerate(audios):
             if audio.dim() != 2 or audio.size(0) != A_DIM:
                 raise ValueError(f"audios[{g}] must be ({A_DIM}, L), got {tuple(audio.shape)}")
-            skips, h = self.latent.audio_encoder(pad_to_multiple(audio.to(torch.float32), self.latent.chunk_size)[None])
-            s = self.style.sample(labels[g]) if s_init is None else self.style.sample(labels[g], s_init=s_init[g])
-            enc.append((audio.size(-1), skips, h, s))
-        zs = self.diffusion.sample_many([e[2] for e in enc], [e[3] for e in enc], num_steps, x_init=x_init)
-        out = []
-        for (L, skips, _, s), z in zip(enc, zs):
-            chart, out_labels = self.latent.decode(z, s, skips=skips)
-            out.append((chart[..., :L], out_labels))
-        return out
+        c, dev = self.latent.chunk_size, audios[0].device
+        Ls = [a.size(-1) for a in audios]
+        Lps = [-(-L // c) * c for L in Ls]
+        audio = torch.zeros(G, A_DIM, max(Lps), device=dev)
+        for g, a in enumerate(audios):
+            audio[g, :, :Lps[g]] = pad_to_multiple(a.to(torch.float32), c)
+        skips, h = self.latent.audio_encoder(audio, lengths=Lps)
+        ss = self.style.sample_many(labels, s_init=s_init)
+        zs = self.diffusion.sample_many([h[g:g + 1, :, :Lps[g] // c] for g in range(G)], ss, num_steps, x_init=x_init)
+        return [(chart[..., :L], out_labels) for (chart, out_labels), L in zip(self._decode_songs(zs, ss, skips, Lps), Ls)]
+
+    def _decode_songs(self, zs: Sequence[torch.Tensor], ss: Sequence[torch.Tensor], skips: Sequence[torch.Tensor], Lps: Sequence[int]
+                      ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """The decoder stage of sample_many: song g's latents zs[g] (B_g, E, Lps[g] / chunk), styles ss[g] (B_g, S) and row g of the batched
+        skips -> (chart (B_g, 9, Lps[g]), labels (B_g, 5)) per song.  In bf16 one varlen call decodes every song.  In fp32 the decoder's
+        GEMMs are compute bound, and a batched call would run them over every song's padding up to the longest song (4 rows per
+        difficulty); there a loop of per-song calls is faster (profiles/r08_ldm_many.txt), and it reads each song's skips in place."""
+        G, dev = len(zs), zs[0].device
+        if self.latent._dtype() == torch.float32:
+            out = []
+            for g in range(G):
+                sk = [t[g:g + 1, :, :Lps[g] // self.args.stride ** i] for i, t in enumerate(skips)]
+                out.append(self.latent.decode(zs[g], ss[g], skips=sk))
+            return out
+        offs = [0]
+        for s in ss:
+            offs.append(offs[-1] + s.shape[0])
+        z = torch.zeros(offs[-1], zs[0].shape[1], skips[-1].shape[-1] // self.args.stride, device=dev)
+        for g in range(G):
+            z[offs[g]:offs[g + 1], :, :zs[g].shape[-1]] = zs[g]
+        chart, out_labels = self.latent.decode(z, torch.cat(ss, 0), skips=skips, lengths=Lps, offs=offs)
+        return [(chart[offs[g]:offs[g + 1]], out_labels[offs[g]:offs[g + 1]]) for g in range(G)]
 
 
 def load_inference(model_path: str, device="cuda") -> LDM:

@@ -578,3 +578,63 @@ def attn_pool(scores, values, out, B, L, heads, hd):
     _f32(out)
     _lib.lib().od_attn_pool(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), B, L, heads, hd,
                             _stream(scores))
+
+
+# ---------------------------------------------------------------- latent model, varlen forms (lens: device int32 [B], the valid
+# frames of each sequence at the level the call reads; frames past them come back as exact zeros)
+def _lens(lens, B):
+    _i32(lens)
+    assert lens.dim() == 1 and lens.shape[0] == B and lens.is_contiguous(), "lens must be a contiguous int32 [B]"
+
+
+def spec_features_conv_varlen(audio, w1, b1, g1, w2, b2, g2, out, lens, eps=1e-6):
+    B, F, L = audio.shape
+    _f32(audio, w1, b1, g1, w2, b2, g2)
+    _lens(lens, B)
+    _lib.lib().od_spec_features_conv_varlen(dt_code(out.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2),
+                                            _p(out), _ld(out), _p(lens), B, F, L, eps, _stream(audio))
+
+
+def rmsnorm_affine_film_varlen(x, gamma, ssg, y, lens, B, L, act=OD_ACT_NONE, eps=1e-6):
+    _f32(gamma, ssg)
+    _lens(lens, B)
+    _lib.lib().od_rmsnorm_affine_film_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(y), _ld(y), _p(lens), B, L,
+                                             x.shape[1], eps, act, _stream(x))
+
+
+def unet_mixer_varlen(x, p, prow, gx, gamma, xo, B, L, eps=1e-6):
+    """unet_mixer where decoder row b reads frame l of skip row prow[b] (device int32 [B])."""
+    _f32(gamma)
+    _lens(prow, B)
+    _lib.lib().od_unet_mixer_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(p), _ld(p), _p(prow), _p(gx), _ld(gx), _p(gamma),
+                                    _p(xo), _ld(xo), B, L, x.shape[1], eps, _stream(x))
+
+
+def unet_down_varlen(x, w, bias, y, lens, B, Lo, stride):
+    """lens: valid frames at the INPUT level (Lo * stride)."""
+    _f32(w, bias)
+    _lens(lens, B)
+    _lib.lib().od_unet_down_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Lo, x.shape[1],
+                                   stride, _stream(x))
+
+
+def unet_up_varlen(x, w, bias, y, lens, B, Li, stride):
+    """lens: valid frames at the INPUT level (Li)."""
+    _f32(w, bias)
+    _lens(lens, B)
+    _lib.lib().od_unet_up_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Li, x.shape[1],
+                                 stride, _stream(x))
+
+
+def chart_head_varlen(x, W, bias, out, lens, B, L, n_sigmoid, rms=False, eps=1e-6):
+    _f32(W, bias, out)
+    _lens(lens, B)
+    _lib.lib().od_chart_head_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(out), _p(lens), B, L, x.shape[1],
+                                    W.shape[0], n_sigmoid, int(rms), eps, _stream(x))
+
+
+def attn_pool_varlen(scores, values, out, lens, B, L, heads, hd):
+    _f32(out)
+    _lens(lens, B)
+    _lib.lib().od_attn_pool_varlen(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), _p(lens), B, L,
+                                   heads, hd, _stream(scores))

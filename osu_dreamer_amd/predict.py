@@ -56,7 +56,7 @@ def predict_many(model_path: str, specs: Sequence[np.ndarray], diff: Sequence[Se
     """`predict` for several spectrograms, the denoiser sampler batched over all of them: one (pred_signals, pred_labels) per spec.
     With `seed`, song g's noise is drawn right after torch.manual_seed(seed), in `predict`'s order (style noise, then latent noise)."""
     from . import _lib
-    from .ldm import load_inference, pad_to_multiple
+    from .ldm import load_inference
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
     labels = np.asarray(diff, dtype=np.float32)
@@ -75,8 +75,9 @@ def predict_many(model_path: str, specs: Sequence[np.ndarray], diff: Sequence[Se
         if seed is not None:
             B, S, E = lab.shape[0], model.style.style_dim, model.diffusion.emb_dim
             s_init, x_init = [], []
+            c = model.latent.chunk_size
             for a in audios:
-                Lz = model.latent.audio_encoder(pad_to_multiple(a, model.latent.chunk_size)[None])[1].shape[-1]
+                Lz = -(-a.shape[-1] // c)                    # the audio encoder's output length: ceil(L / chunk_size)
                 torch.manual_seed(seed)
                 s_init.append(torch.randn(B, S, device=dev))
                 x_init.append(torch.randn(B, E, Lz, device=dev))

@@ -4,14 +4,15 @@
 Same constructor, state-dict keys (`rff.W`, `rff.b` buffers included), `forward(st, labels) -> (u, v)`,
 `compute_conditioning(labels)` and `sample(labels, num_steps=16)`.  The conditioning and every FiLM
 (`films[i](c)`) depend only on the labels, so `sample` computes them once instead of on each of its
-`num_steps + 1` evaluations; the step body is captured into a hipGraph like the denoiser's.  Training of
+`num_steps + 1` evaluations; the step body is captured into a hipGraph like the denoiser's.  `sample_many(labels_list)`
+samples several songs' label batches as one evaluation batch, each song with its own step size.  Training of
 the style model is out of scope (inference only; parameters do not receive gradients here).
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import nn
@@ -81,10 +82,10 @@ class StyleModel(nn.Module):
         self._buf_gen = 0          # bumped on every (re)allocation: a captured graph holding old addresses is stale
 
     # ------------------------------------------------------------------
-    def _b(self, name, shape, like):
+    def _b(self, name, shape, like, dtype=torch.float32):
         t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.device != like.device:
-            t = torch.zeros(shape, dtype=torch.float32, device=like.device)
+        if t is None or tuple(t.shape) != tuple(shape) or t.device != like.device or t.dtype != dtype:
+            t = torch.zeros(shape, dtype=dtype, device=like.device)
             self._buf[name] = t
             self._buf_gen += 1
         return t
@@ -173,3 +174,64 @@ class StyleModel(nn.Module):
             for _ in range(num_steps):
                 step()
         return xs.clone()
+
+    @torch.no_grad()
+    def sample_many(self, labels_list: Sequence[torch.Tensor], num_steps: int = 16,
+                    s_init: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+        """`sample` for G songs in one evaluation batch: labels_list[g] (B_g, 5) -> one (B_g, style_dim) per song.  The step size eta is
+        computed per song over that song's rows (as its own `sample` computes it), and each song steps with its own.  Without `s_init`,
+        the starting noise is drawn per song in song order: the draws G `sample` calls would make.  The loop is captured into one
+        hipGraph per (rows, songs) shape; the song offsets are device data, not part of the graph's key."""
+        G = len(labels_list)
+        if G == 0 or (s_init is not None and len(s_init) != G):
+            raise ValueError("sample_many needs one label batch per song (and one s_init per song when given)")
+        dev, S = labels_list[0].device, self.style_dim
+        Bs = [int(lab.shape[0]) for lab in labels_list]
+        offs = [0]
+        for n in Bs:
+            offs.append(offs[-1] + n)
+        B = offs[-1]
+        inits = []
+        for g in range(G):
+            sg = torch.randn(Bs[g], S, device=dev) if s_init is None else s_init[g].detach().float()
+            if tuple(sg.shape) != (Bs[g], S):
+                raise ValueError(f"s_init[{g}] must be ({Bs[g]}, {S}), got {tuple(sg.shape)}")
+            inits.append(sg)
+        labels = torch.cat([lab.detach().float() for lab in labels_list], 0)
+        W = self._w()
+        ssgs = self._films(self.compute_conditioning(labels), W)          # label-only: once per call
+        u, eta = self._b("smpm.u", (B,), labels), self._b("smpm.eta", (G, 2), labels)
+        v = self._b("smpm.v", (B, S), labels)
+        x = self._b("smpm.s", (B, S, 1), labels)
+        offs_d = self._b("smpm.offs", (G + 1,), labels, torch.int32)
+        lens_d = self._b("smpm.lens", (B,), labels, torch.int32)        # one frame per row
+        host = torch.tensor(offs + [1] * B, dtype=torch.int32)
+        if dev.type == "cuda":
+            host = host.pin_memory()
+        offs_d.copy_(host[:G + 1], non_blocking=True)
+        lens_d.copy_(host[G + 1:], non_blocking=True)
+        x.copy_(torch.cat(inits, 0).view(B, S, 1))
+        xs = x.view(B, S)
+        self._eval(xs, ssgs, W, u, v)
+        ops.sampler_eta_groups(u, offs_d, eta, self.c0, num_steps)
+
+        def step():
+            self._eval(xs, ssgs, W, u, v)
+            ops.sampler_step_varlen(x, u, v.view(B, S, 1), eta, lens_d, offs_d)
+
+        if self.use_graph and dev.type == "cuda" and num_steps > 1:
+            from .graph import CapturedLoop
+            key = ("many", B, G, dev, self._buf_gen, tuple(t.data_ptr() for t in W.values()))
+            if getattr(self, "_graph", None) is None or self._graph[0] != key:
+                if getattr(self, "_graph", None) is not None:
+                    self._graph[1].close()
+                self._graph = (key, CapturedLoop(step, dev))
+            loop = self._graph[1]
+            loop.begin()
+            for _ in range(num_steps):
+                loop.replay()
+            loop.end()
+        else:
+            for _ in range(num_steps):
+                step()
+        return [xs[offs[g]:offs[g + 1]].clone() for g in range(G)]
