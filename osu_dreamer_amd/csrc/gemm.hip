@@ -978,11 +978,15 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const T* __restrict__ G, i
                 ra[i] = (mv && k0 + cc < K) ? *(const u32x4*)(A + (size_t)m * lda + k0 + cc) : (u32x4)(0u);
             }
             if (do_bias) {
+                // a chunk that straddles column N brings in the neighbour's columns: they stay out of the sums (a non-finite one would
+                // set the block's `bad` word and turn every bias of the tile into NaN)
+                const int cc = (tid % CPR) * CH;                 // the same for every i (256 is a multiple of CPR)
 #pragma unroll
                 for (int i = 0; i < NCH; i++) {
                     const T* pg = (const T*)&rg[i];
 #pragma unroll
-                    for (int e = 0; e < CH; e++) bsum[e] += od_t<T>::ld(pg + e);
+                    for (int e = 0; e < CH; e++)
+                        if (n0 + cc + e < N) bsum[e] += od_t<T>::ld(pg + e);
                 }
             }
         };

@@ -89,4 +89,28 @@ def block_rel_l2(a, b, rows=64, floor=1e-3, scale=None, floor_max=1e-5):
     return float(flat[worst]), glob, tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), blk.shape))
 
 
+def tile_errors(a, b, tr, tc, floor=1e-3, scale=None, floor_max=1e-5):
+    """block_errors over 2-D output tiles: relative L2 per (tr x tc) tile of the matrices a, b (M, N) — the last tile row / column may be
+    ragged — and over everything, with the same denominator floors and `scale` as block_errors.
+    Returns (per-tile errors of shape (ceil(M / tr), ceil(N / tc)), global error)."""
+    a, b = a.detach().double(), b.detach().double()
+    M, N = a.shape
+    tm, tn = (M + tr - 1) // tr, (N + tc - 1) // tc
+    pad = (0, tn * tc - N, 0, tm * tr - M)
+    d = torch.nn.functional.pad((a - b).pow(2), pad)
+    r = torch.nn.functional.pad((b if scale is None else scale.double()).pow(2), pad)
+    err = d.reshape(tm, tr, tn, tc).sum((1, 3)).sqrt()
+    ref = r.reshape(tm, tr, tn, tc).sum((1, 3)).sqrt()
+    den = ref.clamp_min(max(floor * float(ref.flatten().median()), floor_max * float(ref.max())) + 1e-300)
+    return err / den, float(d.sum().sqrt() / (r.sum().sqrt() + 1e-300))
+
+
+def tile_rel_l2(a, b, tr, tc, floor=1e-3, scale=None, floor_max=1e-5):
+    """tile_errors reduced: (max tile error, global error, (tile row, tile column) of the worst tile).  NaN anywhere counts as the worst."""
+    blk, glob = tile_errors(a, b, tr, tc, floor, scale, floor_max)
+    flat = blk.flatten()
+    worst = int(torch.nan_to_num(flat, nan=float("inf")).argmax())
+    return float(flat[worst]), glob, (worst // blk.shape[1], worst % blk.shape[1])
+
+
 TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2}
