@@ -937,7 +937,10 @@ extern "C" int od_rmsnorm_gate_residual_film_dwconv(int dtype, const void* x, in
     if (C > 512 || (ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9)) return OD_ERR_UNSUPPORTED;
     if (!x || !h || !xo || !y || !conv_w || !conv_b || xo == x || xo == h) return OD_ERR_ARG;       // the halo frames re-read x and h: xo must not alias them
     // a wave walks 32 frames (2 R / 32 of halo re-reads); launches too small to cover the chip that way (the sampler: B L = 4460) take runs of 8
-    const bool small = (long)B * ((L + 31) / 32) < 2048;
+#ifndef OD_FD_SMALL_RUNS
+#define OD_FD_SMALL_RUNS 2048           // 32-frame runs below which the launch takes runs of 8 (the emulator build lowers it to reach both)
+#endif
+    const bool small = (long)B * ((L + 31) / 32) < OD_FD_SMALL_RUNS;
     const int run = small ? 8 : 32;
     dim3 grid((unsigned)((L + 4 * run - 1) / (4 * run)), (unsigned)B);
 #define FD_GO2(T_, KS_, RUN_) OD_LAUNCH((rmsnorm_gate_res_film_dwconv_kernel<T_, KS_, RUN_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, \
