@@ -319,6 +319,23 @@ int od_style_conditioning(const float* labels, const float* rff_w, const float* 
  * and rms_norm at :99. */
 int od_rmsnorm_rows(const float* x, const float* gamma, float* y, int M, int C, float eps, void* stream);
 
+/* ---- style-model training (models/style/train.py:48-91; the rest of the step reuses od_make_xt / od_loss_grad / od_loss_finalize with
+ *      L = 1, the L = 1 row-norm backwards, od_linear_small_bwd / od_gemm_nt / od_gemm_tn and od_uhead_tail_bwd) */
+/* backward of od_style_conditioning given dc[B,H]:  dcond_w[n,f,h] += sum_b [label_bn >= 0] rff(label_bn/10)[f] dc[b,h];
+ * dcond_b[n,h] += the same without the rff factor;  dnull_labels[n,h] += sum_b [label_bn < 0] dc[b,h].  The Fourier features are
+ * recomputed; rows are selected by the label's sign (a masked label's feature is never read) and summed over b in a fixed order without
+ * atomics: bit-identical from run to run.  replaces: autograd of style/model.py:77-80. */
+int od_style_conditioning_bwd(const float* labels, const float* rff_w, const float* rff_b, const float* dc, float* dcond_w,
+                              float* dcond_b, float* dnull_labels, int B, int NL, int F, int H, void* stream);
+/* backward of od_rmsnorm_rows: dx[M,C] (+= if accumulate_dx) = d/dx of x * rsqrt(mean_c x^2 + eps) (* gamma) under dy[M,C];
+ * dgamma[C] += sum_m dy * xhat (NULL when gamma is NULL), summed over the rows in a fixed order without atomics.
+ * replaces: autograd of nn.RMSNorm at style/model.py:50,98 and of rms_norm at :99. */
+int od_rmsnorm_rows_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, int M, int C, float eps,
+                        int accumulate_dx, void* stream);
+/* dst[n] (dst_dtype) = src[n] (src_dtype), OD_F32 <-> OD_BF16: the boundary between the step's fp32 pieces (proj_in, the heads, the loss)
+ * and its bf16 GEMM blocks.  replaces: the casts autocast inserts around nn.Linear at style/model.py:91-99. */
+int od_cast_rows(int src_dtype, const void* src, int dst_dtype, void* dst, long n, void* stream);
+
 /* ---- latent model, inference path (models/latent/{spec_features,unet,model}.py; LDM.sample's steps either
  *      side of diffusion.sample, inference/model.py:48,51).  Frame-major [B*L][C] activations; C = h_dim must be a
  *      power of two in 8..512.  The SwiGLU body of each block is od_dwconv + od_gemm_nt + od_swiglu_rmsnorm. ---- */

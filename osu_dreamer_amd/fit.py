@@ -1,4 +1,4 @@
-"""`fit-denoiser` — the training shell around `DiffusionTrainer`.
+"""`fit-denoiser` / `fit-style` — the training shell around `DiffusionTrainer` and `StyleTrainer`.
 
 The reference drives its LightningModule with `LightningCLI` + `pytorch_lightning.Trainer`
 (osu_dreamer/scripts/fit_denoiser.py:17-32) configured by models/diffusion/model.yml:3-40.
@@ -14,6 +14,10 @@ that config uses, calling the same hooks in the same order:
 Checkpoints keep Lightning's layout (`state_dict`, `hyper_parameters`, `optimizer_states`,
 `lr_schedulers`, `global_step`, `epoch`) so `export-inference` (models/inference/artifact.py)
 reads them unchanged.
+
+`fit-style` (osu_dreamer/scripts/fit_style.py, models/style/model.yml) drives `StyleTrainer` through the same shell: the checkpoint
+monitor is `val/energy_dist` (mode min), and validation goes through the module's epoch hooks (on_validation_epoch_start /
+validation_step / on_validation_epoch_end), which log every value themselves.  It trains on one device, as the reference does.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ from .model import BackboneArgs, DiffusionModelArgs
 from .train import DiffusionTrainer
 
 DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "model.yml")
+DEFAULT_STYLE_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "style.yml")
 
 
 def seed_everything(seed) -> int:
@@ -59,7 +64,7 @@ class Trainer:
                  gradient_clip_val: Optional[float] = None, log_every_n_steps: int = 5,
                  val_check_interval: Optional[int] = None, limit_val_batches: Optional[int] = None,
                  default_root_dir: str = "runs/denoiser", accelerator: str = "gpu", devices: int = 1,
-                 enable_checkpointing: bool = True, **_ignored):
+                 enable_checkpointing: bool = True, monitor: str = "val/loss", **_ignored):
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.precision = str(precision)
         self.gradient_clip_val = gradient_clip_val
@@ -68,6 +73,7 @@ class Trainer:
         self.limit_val_batches = limit_val_batches
         self.root = default_root_dir
         self.enable_checkpointing = enable_checkpointing
+        self.monitor = monitor                        # ModelCheckpoint(monitor=..., mode=min, save_top_k=1)
         self.global_step, self.epoch = 0, 0
         self.best_val = float("inf")
         # `devices: N` = N ranks, one per GPU (model.yml:11).  The ranks are started by the CLI (`python -m osu_dreamer_amd
@@ -113,6 +119,17 @@ class Trainer:
         n = 0
         was_training = module.training
         module.eval()                                 # Lightning runs validation in eval mode (Dropout1d off)
+        if getattr(module, "validates_by_epoch", False):
+            # the module gathers its batches and logs at the end of the validation epoch (StyleTrainer, style/train.py:111-150)
+            module.on_validation_epoch_start()
+            for i, batch in enumerate(datamodule.val_dataloader()):
+                if self.limit_val_batches is not None and i >= self.limit_val_batches:
+                    break
+                module.validation_step(self._to(batch, device), i)
+            with self._autocast(device):
+                logs = module.on_validation_epoch_end()
+            module.train(was_training)
+            return {k: float(v) for k, v in logs.items()}
         for i, batch in enumerate(datamodule.val_dataloader()):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
@@ -131,7 +148,7 @@ class Trainer:
         elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
             device = torch.device("cpu")     # test-suite only: kernels bound to the SIMT emulator build
         else:
-            raise RuntimeError("fit-denoiser needs an MI355X: osu_dreamer_amd has no CPU path")
+            raise RuntimeError("training needs an MI355X: osu_dreamer_amd has no CPU path")
         reducer, own_group = None, False
         if self.world > 1:
             import torch.distributed as dist
@@ -144,22 +161,24 @@ class Trainer:
         except BaseException:
             # failure (possibly a dead peer): nothing that waits for the device or for other ranks — abort the RCCL communicator and let
             # the exception end the process; the launcher (torchrun agent) then stops the remaining ranks and returns non-zero
-            reducer = getattr(module.diffusion, "_reducer", None)
+            net = getattr(module, "diffusion", None)
+            reducer = getattr(net, "_reducer", None)
             if reducer is not None:
                 try:
                     reducer.close(abort=True)
                 except Exception:
                     pass
-                module.diffusion._reducer = None
+                net._reducer = None
             raise
         # orderly teardown: drain the device, destroy the communicator the C ABI created, then the process group — but only a group this
         # call initialised (left to interpreter exit the order is arbitrary and RCCL can hang or abort there)
         if device.type == "cuda":
             torch.cuda.synchronize()
-        reducer = getattr(module.diffusion, "_reducer", None)
+        net = getattr(module, "diffusion", None)
+        reducer = getattr(net, "_reducer", None)
         if reducer is not None:
             reducer.close()
-            module.diffusion._reducer = None
+            net._reducer = None
         if own_group:
             import torch.distributed as dist
             dist.destroy_process_group()
@@ -169,7 +188,7 @@ class Trainer:
         reducer = None
         module.gradient_clip_val = self.gradient_clip_val
         module.to(device)
-        if self.precision.startswith("16"):
+        if self.precision.startswith("16") and hasattr(module, "diffusion"):
             for m in (module.diffusion, module.diffusion_ema.module):
                 m.attn_dtype = torch.float16
         cfg = module.configure_optimizers()
@@ -183,6 +202,8 @@ class Trainer:
             self.best_val = ck.get("best_val", float("inf"))
         from .ddp import StepAgreement
         if self.world > 1:
+            if not hasattr(module, "diffusion"):
+                raise RuntimeError("data-parallel training is implemented for the denoiser only (GradBucketReducer follows its arena's segments)")
             from .ddp import GradBucketReducer
             reducer = GradBucketReducer(module.diffusion)
             reducer.broadcast_state(opt, module.diffusion_ema, src=0)     # weights, AdamW moments, EMA: rank 0's
@@ -240,8 +261,8 @@ class Trainer:
         self.history.append({"step": self.global_step, **val})
         with open(os.path.join(self.root, "metrics.jsonl"), "a") as f:
             f.write(json.dumps({"step": self.global_step, **val}) + "\n")
-        if self.enable_checkpointing and val.get("val/loss", float("inf")) < self.best_val:
-            self.best_val = val["val/loss"]
+        if self.enable_checkpointing and val.get(self.monitor, float("inf")) < self.best_val:
+            self.best_val = val[self.monitor]
             self.save_checkpoint(os.path.join(self.root, "checkpoints", "best.ckpt"), module, opt, sched)
 
 
@@ -279,12 +300,45 @@ def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, 
     return module, trainer
 
 
+def build_style_from_config(cfg: Dict[str, Any]):
+    from .style_train import StyleTrainer
+    m = dict(cfg["model"])
+    m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))       # models/style/model.yml leaves the schedule at its defaults
+    t = dict(cfg.get("trainer", {}))
+    for k in ("callbacks", "logger", "accumulate_grad_batches", "enable_progress_bar", "enable_model_summary", "benchmark"):
+        t.pop(k, None)
+    t.setdefault("monitor", "val/energy_dist")
+    t.setdefault("default_root_dir", "runs/style")
+    if launch.parse_devices(t.get("devices", 1)) > 1:
+        raise RuntimeError(f"fit-style trains on one device (trainer.devices={t['devices']}): the reference trains the style model on one "
+                           "GPU, and the gradient exchange (GradBucketReducer) is tied to the denoiser's arena")
+    return StyleTrainer(**m), Trainer(**t)
+
+
+def fit_style(config: str = DEFAULT_STYLE_CONFIG, ckpt_path: Optional[str] = None, **overrides):
+    """begin a training run for the style model (reference: scripts/fit_style.py:17-32)."""
+    with open(config) as f:
+        cfg = yaml.safe_load(f)
+    for k, v in overrides.items():
+        sec, key = k.split("__")
+        cfg.setdefault(sec, {})[key] = v
+    if cfg.get("seed_everything") not in (None, False):
+        seed_everything(cfg["seed_everything"])
+    module, trainer = build_style_from_config(cfg)
+    data = LatentDataModule(**cfg["data"])
+    trainer.fit(module, data, ckpt_path=ckpt_path)
+    return module, trainer
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="osu_dreamer_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     f = sub.add_parser("fit-denoiser", help="begin a training run for the diffusion model")
     f.add_argument("-c", "--config", default=DEFAULT_CONFIG)
     f.add_argument("--ckpt-path", default=None)
+    fs = sub.add_parser("fit-style", help="begin a training run for the style model")
+    fs.add_argument("-c", "--config", default=DEFAULT_STYLE_CONFIG)
+    fs.add_argument("--ckpt-path", default=None)
     from . import encode_latents as encode_cmd
     from . import predict as predict_cmd
     encode_cmd.add_parser(sub)
@@ -294,6 +348,9 @@ def main(argv=None):
         return predict_cmd.run(a)
     if a.cmd == "encode-latents":
         return encode_cmd.run(a)
+    if a.cmd == "fit-style":
+        fit_style(a.config, a.ckpt_path)
+        return
     if a.cmd == "fit-denoiser":
         with open(a.config) as fh:
             devices = launch.parse_devices((yaml.safe_load(fh).get("trainer") or {}).get("devices", 1))

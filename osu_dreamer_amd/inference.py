@@ -7,7 +7,8 @@ Two artefacts exist upstream:
     `hparams` {emb_dim, style_dim, latent_args{h_dim...}, diffusion_args, ...} and a `state_dict` whose
     denoiser entries are the EMA weights re-keyed to `diffusion.*`.
 Both load into `osu_dreamer_amd.model.DiffusionModel` unchanged because parameter names/shapes are the
-reference's.  Only the denoiser is constructed; the latent and style models are out of scope.
+reference's.  `style_from_checkpoint` does the same for a fit-style `.ckpt` (`style.*`, `style_ema.module.*`,
+`hyper_parameters.style_dim` / `style_args`).
 """
 from __future__ import annotations
 
@@ -60,5 +61,19 @@ def denoiser_from_inference_artifact(path: str, device="cuda") -> DiffusionModel
     a_dim = la["h_dim"] if isinstance(la, dict) else la.h_dim          # inference/model.py:32
     model = DiffusionModel(hp["emb_dim"], a_dim, hp["style_dim"], _args(hp["diffusion_args"]))
     sd = {k[len("diffusion."):]: v for k, v in art["state_dict"].items() if k.startswith("diffusion.")}
+    model.load_state_dict(sd)
+    return model.to(device).eval()
+
+
+def style_from_checkpoint(path: str, use_ema: bool = True, device="cuda"):
+    """StyleModel (frozen, inference) from a fit-style `.ckpt` (reference's or ours)."""
+    from .style import StyleModel, StyleModelArgs
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    hp = ck["hyper_parameters"]
+    sa = hp["style_args"]
+    sa = sa if isinstance(sa, StyleModelArgs) else dataclass_from_dict(StyleModelArgs, dict(sa) if isinstance(sa, dict) else vars(sa))
+    model = StyleModel(hp["style_dim"], sa)
+    prefix = "style_ema.module." if use_ema else "style."
+    sd = {k[len(prefix):]: v for k, v in ck["state_dict"].items() if k.startswith(prefix)}
     model.load_state_dict(sd)
     return model.to(device).eval()

@@ -529,6 +529,31 @@ def rmsnorm_rows(x, gamma, y, eps):
     _lib.lib().od_rmsnorm_rows(_p(x), _p(gamma), _p(y), M, C, eps, _stream(x))
 
 
+def style_conditioning_bwd(labels, rff_w, rff_b, dc, dcond_w, dcond_b, dnull_labels):
+    """dcond_w / dcond_b / dnull_labels += the conditioning's parameter gradients under dc (B, H)."""
+    B, NL = labels.shape
+    F, H = dcond_w.shape[1], dcond_w.shape[2]
+    _f32(labels, rff_w, rff_b, dc, dcond_w, dcond_b, dnull_labels)
+    assert tuple(dc.shape) == (B, H) and rff_w.numel() == F and rff_b.numel() == F
+    assert tuple(dcond_w.shape) == (NL, F, H) and tuple(dcond_b.shape) == (NL, H) and tuple(dnull_labels.shape) == (NL, H)
+    _lib.lib().od_style_conditioning_bwd(_p(labels), _p(rff_w), _p(rff_b), _p(dc), _p(dcond_w), _p(dcond_b), _p(dnull_labels),
+                                         B, NL, F, H, _stream(labels))
+
+
+def rmsnorm_rows_bwd(x, gamma, dy, dx, dgamma, eps, accumulate_dx=False):
+    """dx (+)= backward of rmsnorm_rows under dy; dgamma += (None when gamma is None)."""
+    M, C = x.shape
+    _f32(x, gamma, dy, dx, dgamma)
+    assert dy.shape == x.shape == dx.shape and (gamma is None or gamma.numel() == C) and (dgamma is None or dgamma.numel() == C)
+    _lib.lib().od_rmsnorm_rows_bwd(_p(x), _p(gamma), _p(dy), _p(dx), _p(dgamma), M, C, eps, int(accumulate_dx), _stream(x))
+
+
+def cast_rows(src, dst):
+    """dst = src converted between fp32 and bf16 (same shape, both contiguous)."""
+    assert src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
+    _lib.lib().od_cast_rows(dt_code(src.dtype), _p(src), dt_code(dst.dtype), _p(dst), src.numel(), _stream(src))
+
+
 # ---------------------------------------------------------------- latent model, inference path
 def spec_features_conv(audio, w1, b1, g1, w2, b2, g2, out, eps=1e-6):
     B, F, L = audio.shape
