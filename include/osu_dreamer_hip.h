@@ -370,6 +370,61 @@ int od_chart_head(int dtype, const void* x, int ldx, const float* W, const float
  * replaces: AttnPool.forward, latent/model.py:33-36 (the two 1x1 convs before it are od_gemm_nt). */
 int od_attn_pool(int dtype, const void* scores, int lds, const void* values, int ldv, float* out, int B, int L, int Hh, int hd,
                  void* stream);
+/* ---- latent model, backward kernels (autograd of the calls above; the SwiGLU body, the 1x1 convs, the films and s reuse od_dwconv_bwd,
+ *      od_swiglu_rmsnorm_bwd, od_gemm_nt / od_gemm_tn, od_linear_small_bwd and od_rmsnorm_rows_bwd).  Same layout as the forward calls; inv_rms
+ *      is recomputed from the row.  Per-frame outputs are written in dtype; every sum over frames or over the batch is fp32 and is ADDED to
+ *      its destination (dgamma, dssg, dw, db, dW).  Those sums are formed in a fixed order without atomics: a block writes one row of
+ *      column partials into `ws` (caller-supplied scratch of ws_floats floats, OD_ERR_ARG when too small) and a second pass adds the rows
+ *      up, so two launches on the same inputs give the same bits.  A block owns od_latent_bwd_block_frames(C) frames; calls with a per-batch
+ *      output (dssg, dp) give every batch row its own blocks: B * ceil(L / frames) partial rows, the others ceil(B * L / frames). ---- */
+/* frames one block of the row backward kernels owns at width C (0 when C is not a power of two in 8..512). */
+int od_latent_bwd_block_frames(int C);
+/* backward of od_rmsnorm_affine_film under dy: dx (+= if accumulate_dx) ; dgamma[C] += ; dssg[b][0:2C] += (scale, shift; ssg NULL: dssg
+ * unused).  act = SiLU: the pre-activation is recomputed.  ws: 3C floats per partial row (per-batch blocks).
+ * replaces: autograd of unet.py:50,53 and spec_features.py:27-28. */
+int od_rmsnorm_affine_film_bwd(int dtype, const void* x, int ldx, const float* gamma, const float* ssg, const void* dy, int lddy, void* dx,
+                               int lddx, int accumulate_dx, float* dgamma, float* dssg, float* ws, long ws_floats, int B, int L, int C,
+                               float eps, int act, void* stream);
+/* backward of od_rmsnorm_affine_gate_residual under dxo: dh ; dgamma[C] += ; dssg[b][2C:3C] += (ssg NULL: unused).  The gradient of x is
+ * dxo itself.  ws: 2C floats per partial row (per-batch blocks).  replaces: autograd of unet.py:28,51. */
+int od_rmsnorm_affine_gate_residual_bwd(int dtype, const void* h, int ldh, const float* gamma, const float* ssg, const void* dxo, int lddxo,
+                                        void* dh, int lddh, float* dgamma, float* dssg, float* ws, long ws_floats, int B, int L, int C,
+                                        float eps, void* stream);
+/* backward of od_unet_mixer under dxo: dgx (dtype) ; dgamma[C] += ; dp = the gradient of the p rows: [B*L][C] of dtype, or, when p_bcast,
+ * fp32 [L][C] summed over the batch in row order.  The gradient of x is dxo itself.  ws: C floats per partial row (per-batch blocks; one
+ * batch row's worth when p_bcast).  replaces: autograd of unet.py:117-126. */
+int od_unet_mixer_bwd(int dtype, const void* p, int ldp, int p_bcast, const void* gx, int ldg, const float* gamma, const void* dxo,
+                      int lddxo, void* dp, int lddp, void* dgx, int lddg, float* dgamma, float* ws, long ws_floats, int B, int L, int C,
+                      float eps, void* stream);
+/* backward of od_unet_down under dy [B*Lo][C]: dx [B*Lo*stride][C] ; dw[C][ks] += ; db[C] += .  ws: C (ks + 1) floats per partial row.
+ * replaces: autograd of unet.py:58-63. */
+int od_unet_down_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx, float* dw, float* db,
+                     float* ws, long ws_floats, int B, int Lo, int C, int stride, void* stream);
+/* backward of od_unet_up under dy [B*Li*stride][C]: dx [B*Li][C] ; dw[C][ks] += ; db[C] += .  ws: C (ks + 1) floats per partial row.
+ * replaces: autograd of unet.py:80-85. */
+int od_unet_up_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx, float* dw, float* db,
+                   float* ws, long ws_floats, int B, int Li, int C, int stride, void* stream);
+/* backward of od_chart_head with n_sigmoid = 0 under dout (B,N,L) fp32: dx [B*L][C] ; dW[N][C] += ; db[N] += (rms != 0: through the
+ * frame's RMS norm).  ws: N (C + 1) floats per partial row.  replaces: autograd of latent/model.py:114; :65-68. */
+int od_chart_head_bwd(int dtype, const void* x, int ldx, const float* W, const float* bias, const float* dout, void* dx, int lddx,
+                      float* dW, float* db, float* ws, long ws_floats, int B, int L, int C, int N, int rms, float eps, void* stream);
+/* backward of od_attn_pool under dout [B][Hh*hd] fp32: dscores [B*L][Hh], dvalues [B*L][Hh*hd] (dtype); hd a power of two in 8..256,
+ * ldv and lddv multiples of 8.  The softmax is recomputed.  replaces: autograd of AttnPool.forward, latent/model.py:33-36. */
+int od_attn_pool_bwd(int dtype, const void* scores, int lds, const void* values, int ldv, const float* dout, void* dscores, int ldds,
+                     void* dvalues, int lddv, int B, int L, int Hh, int hd, void* stream);
+/* backward of od_spec_features_conv under dout [B*L][96] (dtype): dw1[8,1,8,3] += , db1[8] += , dg1[8] += , dw2[32,8,6,3] += , db2[32] += ,
+ * dg2[32] += ; the stage-1 activations are recomputed and the spectrogram takes no gradient.  A block owns 32 frames of one batch row:
+ * ws holds B * ceil(L / 32) partial rows of 4880 floats.  replaces: autograd of spec_features.py:17-26. */
+int od_spec_features_conv_bwd(int dtype, const float* audio, const float* w1, const float* b1, const float* g1, const float* w2,
+                              const float* b2, const float* g2, const void* dout, int ldo, float* dw1, float* db1, float* dg1, float* dw2,
+                              float* db2, float* dg2, float* ws, long ws_floats, int B, int F, int L, float eps, void* stream);
+/* y[n] += x[n] (dtype, contiguous, n % 8 == 0): where the gradients of two readers of one activation meet.
+ * replaces: autograd's accumulation at latent/model.py:98-100 (h feeds style_head and temporal_layer). */
+int od_add_rows(int dtype, const void* x, void* y, long n, void* stream);
+/* dxt[b][e][l] (fp32, channel-major) = sum_c W[c][e] dx[(b,l)][c]: the input gradient od_proj_in_bwd leaves out (E <= 8).
+ * replaces: autograd of latent/model.py:114 (proj_emb) towards z. */
+int od_proj_in_bwd_input(int dtype, const void* dx, int ldx, const float* W, float* dxt, int B, int E, int L, int D, void* stream);
+
 /* ---- varlen forms of the latent kernels: G songs / maps stacked in the padded [B*L][C] layout; lens (device int32 [B]) = valid
  *      frames of sequence b at the level the call reads.  Taps and frames at or past lens[b] read as zero (selected, so padding may
  *      hold NaN) and frames there that the call writes come back as exact zeros.  Valid frames are bit for bit the plain call on

@@ -1,6 +1,7 @@
-// Latent model, inference path (osu_dreamer/models/latent/{spec_features,unet,model}.py): the step either
-// side of diffusion.sample in LDM.sample.  Frame-major [B*L][C] like the denoiser; C = h_dim = 128 is
-// narrower than a wavefront x 8 channels, so here G = C/8 lanes own a frame and a wave walks 64/G frames.
+// Latent model (osu_dreamer/models/latent/{spec_features,unet,model}.py): the inference path, the step either
+// side of diffusion.sample in LDM.sample, and (second half of the file) the backward kernels of the same calls.
+// Frame-major [B*L][C] like the denoiser; C = h_dim = 128 is narrower than a wavefront x 8 channels, so here
+// G = C/8 lanes own a frame and a wave walks 64/G frames.
 // The SwiGLU body of each block reuses od_dwconv / od_gemm_nt / od_swiglu_rmsnorm.  All HBM-bound row work.
 // VL forms (several songs / maps of different lengths in one call): sequence b of the padded [B*L][C] layout is valid for frames
 // < lens[b] (device int32 [B], the lengths AT THE LEVEL the kernel reads); taps and frames past it read as zero, selected, never
@@ -501,6 +502,855 @@ extern "C" int od_attn_pool_varlen(int dtype, const void* scores, int lds, const
     if (!lens) return OD_ERR_ARG;
     DISPATCH_T(dtype, OD_LAUNCH((attn_pool_kernel<T_, true>), dim3(Hh, B), dim3(256), 0, (hipStream_t)stream, (const T_*)scores, lds,
                                 (const T_*)values, ldv, out, L, Hh, hd, lens));
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+// ================================================================================================================================
+// Backward (training) kernels: autograd of the row kernels above.  Same lane layout (G = C/8 lanes own a frame, 16-byte accesses,
+// fp32 arithmetic, inv_rms recomputed from the row that is read anyway).  A block walks BW_NIT passes of 256/G frames; the sums over
+// frames (gamma, FiLM rows, conv taps, head weights) stay in registers across the passes, meet across the block's frame slots in LDS in
+// slot order, and leave as ONE row of column partials per block in the caller's workspace.  partial_sum_kernel then adds the rows of a
+// destination in block order: no atomics anywhere, the same bits on every launch.
+// ================================================================================================================================
+namespace {
+
+constexpr int BW_NIT = 4;        // passes of 256/G frames per block
+constexpr int BW_KS = 9;         // widest resample conv: stride 8 -> 1 + 2*(8/2) taps
+
+inline int bw_frames(int C) { return 256 / (C >> 3) * BW_NIT; }
+inline long bw_blocks(long n, int C) { const int f = bw_frames(C); return (n + f - 1) / f; }
+
+// acc[e] of every lane (frame slot = threadIdx.x / G, channels c..c+7) summed over the block's frame slots, in slot order -> dst[c + e].
+// s_red holds 256 * 8 floats; all 256 threads call it.
+__device__ __forceinline__ void block_colsum(const float (&acc)[8], float* s_red, int G, int C, int c, float* __restrict__ dst) {
+    const int slot = threadIdx.x / G, nslot = 256 / G;
+#pragma unroll
+    for (int e = 0; e < 8; e++) s_red[slot * C + c + e] = acc[e];
+    __syncthreads();
+    for (int t = threadIdx.x; t < C; t += 256) {
+        float s = 0.f;
+        for (int j = 0; j < nslot; j++) s += s_red[j * C + t];
+        dst[t] = s;
+    }
+    __syncthreads();
+}
+
+// out[g * ldo + (col % inner) * sa + (col / inner) * sb] += scale * sum_{j < nb} ws[(g * nb + j) * ncols + col0 + col],  col < n.
+// 16 columns x 16 segments per block: a segment adds its contiguous share of the nb rows in order, the 16 segment sums meet in order.
+__global__ __launch_bounds__(256) void partial_sum_kernel(const float* __restrict__ ws, int nb, int ncols, int col0, float* __restrict__ out,
+                                                          long ldo, int n, int inner, int sa, int sb, float scale) {
+    __shared__ float s_seg[16][17];
+    const int tc = threadIdx.x & 15, seg = threadIdx.x >> 4;
+    const int col = blockIdx.x * 16 + tc, g = blockIdx.y;
+    const int per = (nb + 15) / 16;
+    const int j0 = seg * per, j1 = j0 + per < nb ? j0 + per : nb;
+    float s = 0.f;
+    if (col < n)
+        for (int j = j0; j < j1; j++) s += ws[((size_t)g * nb + j) * ncols + col0 + col];
+    s_seg[seg][tc] = s;
+    __syncthreads();
+    if (seg == 0 && col < n) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; k++) t += s_seg[k][tc];
+        out[(size_t)g * ldo + (size_t)(col % inner) * sa + (size_t)(col / inner) * sb] += scale * t;
+    }
+}
+
+inline void launch_partial_sum(hipStream_t st, const float* ws, int groups, int nb, int ncols, int col0, float* out, long ldo, int n,
+                               int inner, int sa, int sb, float scale) {
+    OD_LAUNCH(partial_sum_kernel, dim3((n + 15) / 16, groups), dim3(256), 0, st, ws, nb, ncols, col0, out, ldo, n, inner, sa, sb, scale);
+}
+
+// frame slot, channel and the block's first frame, for the kernels whose blocks stay inside one batch row (grid: blocks per row x B)
+#define OD_BWD_BLOCK_OF_LANE()                                                  \
+    const int G = C >> 3, rpp = 256 / G;                                        \
+    const int c = (threadIdx.x % G) * 8;                                        \
+    const int l0 = blockIdx.x * rpp * BW_NIT + threadIdx.x / G
+
+// y = act(u), u = x^ gamma (1 + scale[b]) + shift[b], x^ = x inv:   du = dy act'(u);  dshift[b] += du;  dscale[b] += du x^ gamma;
+// dgamma += du (1 + scale) x^;  with g = du gamma (1 + scale):  dx (+)= inv (g - x^ mean_c(g x^)).        partial row: [dgamma | dscale | dshift]
+template <class T>
+__global__ __launch_bounds__(256) void rms_affine_film_bwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ ssg, const T* __restrict__ dy, int lddy,
+                                                                  T* __restrict__ dx, int lddx, int accumulate, float* __restrict__ ws,
+                                                                  int L, int C, float eps, int act) {
+    __shared__ float s_red[2048];
+    OD_BWD_BLOCK_OF_LANE();
+    const int b = blockIdx.y;
+    float g[8], sc[8], sh[8];
+    od_ld8(gamma + c, g);
+#pragma unroll
+    for (int e = 0; e < 8; e++) { sc[e] = 1.f; sh[e] = 0.f; }
+    if (ssg) {
+        float s[8];
+        od_ld8(ssg + (size_t)b * 3 * C + c, s);
+        od_ld8(ssg + (size_t)b * 3 * C + C + c, sh);
+#pragma unroll
+        for (int e = 0; e < 8; e++) sc[e] = 1.f + s[e];
+    }
+    float a_g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a_h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int it = 0; it < BW_NIT; it++) {
+        const int l = l0 + it * rpp;
+        const bool live = l < L;
+        const long m = (long)b * L + (live ? l : L - 1);      // dead lanes shadow the last frame so shuffles stay convergent
+        float v[8], d[8], o[8];
+        od_ld8(x + m * ldx + c, v);
+        od_ld8(dy + m * lddy + c, d);
+        const float inv = rsqrtf(group_sum(sumsq8(v), G) / (float)C + eps);
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            v[e] *= inv;                                       // x^
+            if (act == OD_ACT_SILU) d[e] *= od_silu_grad(v[e] * g[e] * sc[e] + sh[e]);
+            if (live) { a_h[e] += d[e]; a_s[e] += d[e] * v[e] * g[e]; a_g[e] += d[e] * sc[e] * v[e]; }
+            d[e] *= g[e] * sc[e];
+            dot += d[e] * v[e];
+        }
+        dot = group_sum(dot, G) / (float)C;
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] = inv * (d[e] - v[e] * dot);
+        if (live) {
+            if (accumulate) {
+                float old[8];
+                od_ld8(dx + m * lddx + c, old);
+#pragma unroll
+                for (int e = 0; e < 8; e++) o[e] += old[e];
+            }
+            od_st8(dx + m * lddx + c, o);
+        }
+    }
+    float* row = ws + ((size_t)b * gridDim.x + blockIdx.x) * 3 * C;
+    block_colsum(a_g, s_red, G, C, c, row);
+    if (ssg) {
+        block_colsum(a_s, s_red, G, C, c, row + C);
+        block_colsum(a_h, s_red, G, C, c, row + 2 * C);
+    }
+}
+
+// xo = x + h^ gamma (1 + gate[b]), h^ = h inv:   dgamma += dxo (1 + gate) h^;  dgate[b] += dxo gamma h^;
+// with g = dxo gamma (1 + gate):  dh = inv (g - h^ mean_c(g h^)).                                          partial row: [dgamma | dgate]
+template <class T>
+__global__ __launch_bounds__(256) void rms_affine_gate_res_bwd_kernel(const T* __restrict__ h, int ldh, const float* __restrict__ gamma,
+                                                                      const float* __restrict__ ssg, const T* __restrict__ dxo, int lddxo,
+                                                                      T* __restrict__ dh, int lddh, float* __restrict__ ws, int L, int C,
+                                                                      float eps) {
+    __shared__ float s_red[2048];
+    OD_BWD_BLOCK_OF_LANE();
+    const int b = blockIdx.y;
+    float g[8], gt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    od_ld8(gamma + c, g);
+    if (ssg) od_ld8(ssg + (size_t)b * 3 * C + 2 * C + c, gt);
+    float a_g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int it = 0; it < BW_NIT; it++) {
+        const int l = l0 + it * rpp;
+        const bool live = l < L;
+        const long m = (long)b * L + (live ? l : L - 1);
+        float v[8], d[8], o[8];
+        od_ld8(h + m * ldh + c, v);
+        od_ld8(dxo + m * lddxo + c, d);
+        const float inv = rsqrtf(group_sum(sumsq8(v), G) / (float)C + eps);
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            v[e] *= inv;
+            if (live) { a_g[e] += d[e] * (1.f + gt[e]) * v[e]; a_t[e] += d[e] * g[e] * v[e]; }
+            d[e] *= g[e] * (1.f + gt[e]);
+            dot += d[e] * v[e];
+        }
+        dot = group_sum(dot, G) / (float)C;
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] = inv * (d[e] - v[e] * dot);
+        if (live) od_st8(dh + m * lddh + c, o);
+    }
+    float* row = ws + ((size_t)b * gridDim.x + blockIdx.x) * 2 * C;
+    block_colsum(a_g, s_red, G, C, c, row);
+    if (ssg) block_colsum(a_t, s_red, G, C, c, row + C);
+}
+
+// xo = x + p^ gamma gx, p^ = p inv:   dgx = dxo p^ gamma;  dgamma += dxo p^ gx;  with g = dxo gamma gx:  dp = inv (g - p^ mean_c(g p^)).
+// BC (the skip is broadcast): the block's frames are frames of the ONE skip row; a lane walks the batch rows in order, keeps its frame's
+// dp in fp32 registers and writes the sum as fp32.                                                         partial row: [dgamma]
+template <class T, bool BC>
+__global__ __launch_bounds__(256) void mixer_bwd_kernel(const T* __restrict__ p, int ldp, const T* __restrict__ gx, int ldg,
+                                                        const float* __restrict__ gamma, const T* __restrict__ dxo, int lddxo,
+                                                        void* __restrict__ dp_, int lddp, T* __restrict__ dgx, int lddg,
+                                                        float* __restrict__ ws, int B, int L, int C, float eps) {
+    __shared__ float s_red[2048];
+    OD_BWD_BLOCK_OF_LANE();
+    float g[8];
+    od_ld8(gamma + c, g);
+    float a_g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int b0 = BC ? 0 : blockIdx.y, b1 = BC ? B : blockIdx.y + 1;
+    for (int it = 0; it < BW_NIT; it++) {
+        const int l = l0 + it * rpp;
+        const bool live = l < L;
+        const int lr = live ? l : L - 1;
+        float v[8], sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float inv = 0.f;
+        for (int b = b0; b < b1; b++) {
+            const long m = (long)b * L + lr;
+            if (!BC || b == b0) {
+                od_ld8(p + (BC ? (long)lr : m) * ldp + c, v);
+                inv = rsqrtf(group_sum(sumsq8(v), G) / (float)C + eps);
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] *= inv;
+            }
+            float d[8], q[8], o[8];
+            od_ld8(dxo + m * lddxo + c, d);
+            od_ld8(gx + m * ldg + c, q);
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                o[e] = d[e] * v[e] * g[e];
+                if (live) a_g[e] += d[e] * v[e] * q[e];
+                d[e] *= g[e] * q[e];
+                dot += d[e] * v[e];
+            }
+            if (live) od_st8(dgx + m * lddg + c, o);
+            dot = group_sum(dot, G) / (float)C;
+#pragma unroll
+            for (int e = 0; e < 8; e++) sum[e] += inv * (d[e] - v[e] * dot);
+            if (!BC && live) od_st8((T*)dp_ + m * lddp + c, sum);
+        }
+        if (BC && live) od_st8((float*)dp_ + (long)l * lddp + c, sum);
+    }
+    float* row = ws + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * C;
+    block_colsum(a_g, s_red, G, C, c, row);
+}
+
+// sum of w[c+e][k] over k0 <= k <= k1 (the taps that land on one input frame)
+__device__ __forceinline__ void tap_sum(const float* __restrict__ w, int c, int ks, int k0, int k1, float (&ws)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        float s = 0.f;
+        for (int k = k0; k <= k1; k++) s += w[(c + e) * ks + k];
+        ws[e] = s;
+    }
+}
+
+// od_unet_down, gradient of the input: dx[b][l] = (1/s) sum_lo dy[b][lo] (sum of w[k] over the k + j = l - s lo + r, 0 <= j < s)
+template <class T>
+__global__ __launch_bounds__(256) void unet_down_bwd_dx_kernel(const float* __restrict__ w, const T* __restrict__ dy, int lddy,
+                                                               T* __restrict__ dx, int lddx, int B, int Lo, int C, int s) {
+    const int G = C >> 3, r = s / 2, ks = 2 * r + 1, L = Lo * s;
+    const long M = (long)B * L;
+    const long m = (long)blockIdx.x * (256 / G) + threadIdx.x / G;
+    const int c = (threadIdx.x % G) * 8;
+    if (m >= M) return;
+    const int b = (int)(m / L), l = (int)(m % L);
+    const int num = l - (s - 1) - r;
+    const int lo_min = num <= 0 ? 0 : (num + s - 1) / s;
+    const int lo_max = (l + r) / s < Lo - 1 ? (l + r) / s : Lo - 1;
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int lo = lo_min; lo <= lo_max; lo++) {
+        const int t = l - s * lo + r;                         // 0 <= t <= s + ks - 2
+        const int k0 = t - (s - 1) > 0 ? t - (s - 1) : 0, k1 = t < ks - 1 ? t : ks - 1;
+        float d[8], wv[8];
+        od_ld8(dy + ((long)b * Lo + lo) * lddy + c, d);
+        tap_sum(w, c, ks, k0, k1, wv);
+#pragma unroll
+        for (int e = 0; e < 8; e++) acc[e] += wv[e] * d[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) acc[e] /= (float)s;
+    od_st8(dx + m * lddx + c, acc);
+}
+
+// od_unet_down, gradients of the taps and the bias, per output frame: db += dy;  dw[k] += dy (1/s) sum_j x[s lo + j + k - r]  (the 1/s is
+// applied by the second pass).  UP: od_unet_up instead, per output frame l: dw[k] += dy x[(l + k - r) / s].
+// partial row: [dw tap 0 | ... | dw tap ks-1 | db], C columns each
+template <class T, bool UP>
+__global__ __launch_bounds__(256) void unet_resample_bwd_dw_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ dy, int lddy,
+                                                                   float* __restrict__ ws, int B, int Ly, int C, int s) {
+    __shared__ float s_red[2048];
+    const int G = C >> 3, rpp = 256 / G, r = s / 2, ks = 2 * r + 1;
+    const int c = (threadIdx.x % G) * 8;
+    const long M = (long)B * Ly;                              // frames of dy
+    const int Lx = UP ? Ly / s : Ly * s;                      // frames of x per batch row
+    const int Lu = UP ? Ly : Lx;                              // the conv's own length (it runs at the fine level both ways)
+    float a_w[BW_KS][8], a_b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < BW_KS; k++)
+#pragma unroll
+        for (int e = 0; e < 8; e++) a_w[k][e] = 0.f;
+    for (int it = 0; it < BW_NIT; it++) {
+        const long m = ((long)blockIdx.x * BW_NIT + it) * rpp + threadIdx.x / G;
+        if (m >= M) continue;
+        const int b = (int)(m / Ly), ly = (int)(m % Ly);
+        float d[8];
+        od_ld8(dy + m * lddy + c, d);
+#pragma unroll
+        for (int e = 0; e < 8; e++) a_b[e] += d[e];
+        if (UP) {
+#pragma unroll
+            for (int k = 0; k < BW_KS; k++) {
+                const int lu = ly + k - r;
+                if (k >= ks || lu < 0 || lu >= Lu) continue;
+                float v[8];
+                od_ld8(x + ((long)b * Lx + lu / s) * ldx + c, v);
+#pragma unroll
+                for (int e = 0; e < 8; e++) a_w[k][e] += d[e] * v[e];
+            }
+        } else {
+            for (int t = 0; t < s + ks - 1; t++) {
+                const int l = s * ly - r + t;
+                if (l < 0 || l >= Lu) continue;
+                float v[8];
+                od_ld8(x + ((long)b * Lx + l) * ldx + c, v);
+#pragma unroll
+                for (int k = 0; k < BW_KS; k++) {
+                    const int j = t - k;
+                    if (k < ks && j >= 0 && j < s) {
+#pragma unroll
+                        for (int e = 0; e < 8; e++) a_w[k][e] += d[e] * v[e];
+                    }
+                }
+            }
+        }
+    }
+    float* row = ws + (size_t)blockIdx.x * (ks + 1) * C;
+#pragma unroll
+    for (int k = 0; k < BW_KS; k++)
+        if (k < ks) block_colsum(a_w[k], s_red, G, C, c, row + (size_t)k * C);
+    block_colsum(a_b, s_red, G, C, c, row + (size_t)ks * C);
+}
+
+// od_unet_up, gradient of the input: dx[b][li] = sum_l dy[b][l] (sum of w[k] over s li <= l + k - r <= s li + s - 1)
+template <class T>
+__global__ __launch_bounds__(256) void unet_up_bwd_dx_kernel(const float* __restrict__ w, const T* __restrict__ dy, int lddy,
+                                                             T* __restrict__ dx, int lddx, int B, int Li, int C, int s) {
+    const int G = C >> 3, r = s / 2, ks = 2 * r + 1, L = Li * s;
+    const long M = (long)B * Li;
+    const long m = (long)blockIdx.x * (256 / G) + threadIdx.x / G;
+    const int c = (threadIdx.x % G) * 8;
+    if (m >= M) return;
+    const int b = (int)(m / Li), li = (int)(m % Li);
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int l = s * li - r; l <= s * li + s - 1 + r; l++) {
+        if (l < 0 || l >= L) continue;
+        const int k0 = s * li - l + r > 0 ? s * li - l + r : 0;
+        const int k1 = s * li + s - 1 - l + r < ks - 1 ? s * li + s - 1 - l + r : ks - 1;
+        float d[8], wv[8];
+        od_ld8(dy + ((long)b * L + l) * lddy + c, d);
+        tap_sum(w, c, ks, k0, k1, wv);
+#pragma unroll
+        for (int e = 0; e < 8; e++) acc[e] += wv[e] * d[e];
+    }
+    od_st8(dx + m * lddx + c, acc);
+}
+
+// od_chart_head (n_sigmoid = 0): y_n = bias_n + W_n . x;  out_n = y_n k, k = rsqrt(mean_n y^2 + eps) when rms, else y_n.
+// dy_n = k (dout_n - y^_n mean_n(dout y^)) (rms) or dout_n;  dx = sum_n dy_n W_n;  dW_n += dy_n x;  db_n += dy_n.
+// partial row: [dW row 0 | ... | dW row N-1 | db (N)]
+template <class T, int NMAX>
+__global__ __launch_bounds__(256) void chart_head_bwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ W,
+                                                             const float* __restrict__ bias, const float* __restrict__ dout,
+                                                             T* __restrict__ dx, int lddx, float* __restrict__ ws, long M, int L, int C,
+                                                             int N, int rms, float eps) {
+    __shared__ float s_red[2048];
+    const int G = C >> 3, rpp = 256 / G;
+    const int c = (threadIdx.x % G) * 8, slot = threadIdx.x / G;
+    float a_w[NMAX][8], a_b[NMAX];
+#pragma unroll
+    for (int n = 0; n < NMAX; n++) {
+        a_b[n] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) a_w[n][e] = 0.f;
+    }
+    for (int it = 0; it < BW_NIT; it++) {
+        const long m = ((long)blockIdx.x * BW_NIT + it) * rpp + slot;
+        const bool live = m < M;
+        const long mr = live ? m : M - 1;
+        const int b = (int)(mr / L), l = (int)(mr % L);
+        float v[8], dyv[NMAX], ss = 0.f, dd = 0.f;
+        od_ld8(x + mr * ldx + c, v);
+#pragma unroll
+        for (int n = 0; n < NMAX; n++) {
+            dyv[n] = 0.f;
+            if (n >= N) continue;
+            dyv[n] = dout[((size_t)b * N + n) * L + l];
+            if (rms) {
+                float wv[8], s = 0.f;
+                od_ld8(W + (size_t)n * C + c, wv);
+#pragma unroll
+                for (int e = 0; e < 8; e++) s += wv[e] * v[e];
+                s = group_sum(s, G) + bias[n];
+                ss += s * s; dd += dyv[n] * s;                 // y_n is recomputed below rather than held in NMAX more registers
+            }
+        }
+        float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const float k = rms ? rsqrtf(ss / (float)N + eps) : 1.f;
+        const float mean = dd * k / (float)N;                 // mean_n(dout y^)
+#pragma unroll
+        for (int n = 0; n < NMAX; n++) {
+            if (n >= N) continue;
+            float wv[8];
+            od_ld8(W + (size_t)n * C + c, wv);
+            float g = dyv[n];
+            if (rms) {
+                float s = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; e++) s += wv[e] * v[e];
+                s = group_sum(s, G) + bias[n];
+                g = k * (g - s * k * mean);
+            }
+            if (live) {
+                a_b[n] += g;
+#pragma unroll
+                for (int e = 0; e < 8; e++) a_w[n][e] += g * v[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e++) o[e] += g * wv[e];
+        }
+        if (live) od_st8(dx + m * lddx + c, o);
+    }
+    float* row = ws + (size_t)blockIdx.x * N * (C + 1);
+#pragma unroll
+    for (int n = 0; n < NMAX; n++)
+        if (n < N) block_colsum(a_w[n], s_red, G, C, c, row + (size_t)n * C);
+    // db: every lane of a frame holds the same dy_n; the frame's first lane hands it over, `per` outputs a round so that the rpp slots
+    // fit s_red (C = 8: 256 slots x 8, two rounds; wider C: one round of NMAX)
+    const int per = 2048 / rpp < NMAX ? 2048 / rpp : NMAX;
+    for (int n0 = 0; n0 < N; n0 += per) {
+#pragma unroll
+        for (int n = 0; n < NMAX; n++)
+            if (c == 0 && n >= n0 && n < n0 + per) s_red[slot * per + n - n0] = a_b[n];
+        __syncthreads();
+        const int n = n0 + (int)threadIdx.x;
+        if ((int)threadIdx.x < per && n < N) {
+            float s = 0.f;
+            for (int j = 0; j < rpp; j++) s += s_red[j * per + threadIdx.x];
+            row[(size_t)N * C + n] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// AttnPool backward, one block per (b, h); G2 = hd/8 lanes own a frame's head slice.  With p = softmax_l(scores), dot_l = dout . v_l:
+// dv_l = p_l dout;  dscore_l = p_l (dot_l - sum_l' p_l' dot_l').  Block sums (max, denominator, sum p dot) go through LDS trees in a fixed order.
+__device__ __forceinline__ float block_tree(float v, float* red, bool is_max) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] = is_max ? fmaxf(red[t], red[t + s]) : red[t] + red[t + s];
+        __syncthreads();
+    }
+    const float out = red[0];
+    __syncthreads();
+    return out;
+}
+template <class T>
+__global__ __launch_bounds__(256) void attn_pool_bwd_kernel(const T* __restrict__ scores, int lds_, const T* __restrict__ values, int ldv,
+                                                            const float* __restrict__ dout, T* __restrict__ dscores, int ldds,
+                                                            T* __restrict__ dvalues, int lddv, int L, int Hh, int hd) {
+    __shared__ float red[256];
+    const int b = blockIdx.y, h = blockIdx.x, t = threadIdx.x;
+    const int G2 = hd >> 3, fpp = 256 / G2, slot = t / G2, c = (t % G2) * 8;
+    const T* sb = scores + (size_t)b * L * lds_ + h;
+    float mx = -3.0e38f;
+    for (int l = t; l < L; l += 256) mx = fmaxf(mx, od_t<T>::ld(sb + (size_t)l * lds_));
+    mx = block_tree(mx, red, true);
+    float go[8];
+    od_ld8(dout + ((size_t)b * Hh + h) * hd + c, go);
+    float den = 0.f, pd = 0.f;
+    for (int l0 = 0; l0 < L; l0 += fpp) {
+        const int l = l0 + slot;
+        const bool live = l < L;
+        const int lr = live ? l : L - 1;
+        float v[8], dot = 0.f;
+        od_ld8(values + ((size_t)b * L + lr) * ldv + h * hd + c, v);
+#pragma unroll
+        for (int e = 0; e < 8; e++) dot += go[e] * v[e];
+        dot = group_sum(dot, G2);
+        const float ex = __expf(od_t<T>::ld(sb + (size_t)lr * lds_) - mx);
+        if (live && c == 0) { den += ex; pd += ex * dot; }
+    }
+    den = block_tree(den, red, false);
+    pd = block_tree(pd, red, false) / den;                   // sum_l p_l dot_l
+    for (int l0 = 0; l0 < L; l0 += fpp) {
+        const int l = l0 + slot;
+        const bool live = l < L;
+        const int lr = live ? l : L - 1;
+        float v[8], o[8], dot = 0.f;
+        od_ld8(values + ((size_t)b * L + lr) * ldv + h * hd + c, v);
+#pragma unroll
+        for (int e = 0; e < 8; e++) dot += go[e] * v[e];
+        dot = group_sum(dot, G2);
+        const float pl = __expf(od_t<T>::ld(sb + (size_t)lr * lds_) - mx) / den;
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] = pl * go[e];
+        if (live) {
+            od_st8(dvalues + ((size_t)b * L + l) * lddv + h * hd + c, o);
+            if (c == 0) od_t<T>::st(dscores + ((size_t)b * L + l) * ldds + h, pl * (dot - pd));
+        }
+    }
+}
+
+// dxt[b][e][l] = sum_c W[c][e] dx[(b,l)][c]
+template <class T>
+__global__ __launch_bounds__(256) void proj_in_bwd_input_kernel(const T* __restrict__ dx, int ldx, const float* __restrict__ W,
+                                                                float* __restrict__ dxt, long M, int L, int C, int E) {
+    OD_ROW_OF_LANE();
+    float d[8], acc[8];
+    od_ld8(dx + mr * ldx + c, d);
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        float s = 0.f;
+        if (e < E) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) s += W[(size_t)(c + i) * E + e] * d[i];
+        }
+        acc[e] = group_sum(s, G);
+    }
+    const int b = (int)(mr / L), l = (int)(mr % L);
+#pragma unroll
+    for (int e = 0; e < 8; e++)
+        if (e < E && live && c == 0) dxt[((size_t)b * E + e) * L + l] = acc[e];
+}
+
+// SpecFeatures front end, backward (parameters only: the spectrogram takes no gradient).  One block owns SFB_TL frames of one batch row,
+// recomputes stage 1 with a 2-frame halo and stage 2 with a 1-frame halo (the gradient of an owned stage-1 frame comes from the stage-2
+// frames either side), and keeps in LDS: the spectrogram tile, h1, the gradient at conv2's output (dacc2) and one more plane that first
+// holds the g2 terms and then the gradient at conv1's output (dacc1); the g1 terms reuse h1's storage once conv2's weights are done.
+// Every parameter's sum over the block's positions is formed by ONE thread walking the positions in order (gather form, no LDS atomics)
+// and written straight into the block's partial row: [dw1 192 | db1 8 | dg1 8 | dw2 4608 | db2 32 | dg2 32].
+constexpr int SFB_TL = 32;
+constexpr int SFB_W1 = SF_C1 * 8 * 3, SFB_W2 = SF_C2 * SF_C1 * 6 * 3;
+constexpr int SFB_COLS = SFB_W1 + 2 * SF_C1 + SFB_W2 + 2 * SF_C2;
+template <class T>
+__global__ __launch_bounds__(256) void spec_conv_bwd_kernel(const float* __restrict__ audio, const float* __restrict__ w1,
+                                                            const float* __restrict__ b1, const float* __restrict__ g1,
+                                                            const float* __restrict__ w2, const float* __restrict__ b2,
+                                                            const float* __restrict__ g2, const T* __restrict__ dout, int ldo,
+                                                            float* __restrict__ ws, int L, float eps) {
+    __shared__ float s_in[SF_F + 2][SFB_TL + 6];               // freq rows -1..72, frames l0-3 .. l0+TL+2
+    __shared__ float s_h1[SF_C1][SF_A1 + 2][SFB_TL + 4];       // freq rows -1..12, frames l0-2 .. l0+TL+1
+    __shared__ float s_d2[SF_C2][SF_A2][SFB_TL + 2];           // dacc2, frames l0-1 .. l0+TL
+    __shared__ float s_r2[SF_C2 * SF_A2 * SFB_TL];             // g2 terms [c2][a2][t], then dacc1 [cc][a1][t] (the same size)
+    float* s_t1 = &s_h1[0][0][0];                              // g1 terms [cc][a1][t], once h1 is dead
+    const int b = blockIdx.y, l0 = blockIdx.x * SFB_TL, tid = threadIdx.x;
+    const float* ab = audio + (size_t)b * SF_F * L;
+    for (int i = tid; i < (SF_F + 2) * (SFB_TL + 6); i += 256) {
+        const int f = i / (SFB_TL + 6) - 1, t = i % (SFB_TL + 6), l = l0 - 3 + t;
+        s_in[f + 1][t] = (f >= 0 && f < SF_F && l >= 0 && l < L) ? ab[(size_t)f * L + l] : 0.f;
+    }
+    for (int i = tid; i < SF_C1 * 2 * (SFB_TL + 4); i += 256) {   // zero freq border of h1
+        const int cc = i / (2 * (SFB_TL + 4)), rr = (i / (SFB_TL + 4)) % 2, t = i % (SFB_TL + 4);
+        s_h1[cc][rr ? SF_A1 + 1 : 0][t] = 0.f;
+    }
+    __syncthreads();
+    // stage 1 forward: h1 = SiLU(rms(conv1) g1), zero outside the sequence (conv2's time padding)
+    for (int i = tid; i < SF_A1 * (SFB_TL + 4); i += 256) {
+        const int a = i / (SFB_TL + 4), t = i % (SFB_TL + 4), l = l0 - 2 + t;
+        float acc[SF_C1];
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) acc[cc] = b1[cc];
+        for (int fi = 0; fi < 8; fi++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const float v = s_in[6 * a + fi][t + j];
+#pragma unroll
+                for (int cc = 0; cc < SF_C1; cc++) acc[cc] += w1[(cc * 8 + fi) * 3 + j] * v;
+            }
+        float ss = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) ss += acc[cc] * acc[cc];
+        const float inv = rsqrtf(ss / (float)SF_C1 + eps);
+        const bool inside = l >= 0 && l < L;
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) s_h1[cc][a + 1][t] = inside ? od_silu(acc[cc] * inv * g1[cc]) : 0.f;
+    }
+    __syncthreads();
+    // stage 2 forward and its backward down to conv2's output: dacc2 (0 outside the sequence) and the g2 terms of the owned frames
+    for (int i = tid; i < SF_A2 * (SFB_TL + 2); i += 256) {
+        const int a = i / (SFB_TL + 2), t = i % (SFB_TL + 2), l = l0 - 1 + t;
+        const bool inside = l >= 0 && l < L, owned = inside && t >= 1 && t <= SFB_TL;
+        float acc[SF_C2];
+#pragma unroll
+        for (int c2 = 0; c2 < SF_C2; c2++) acc[c2] = b2[c2];
+        if (inside) {
+#pragma unroll 1
+            for (int cc = 0; cc < SF_C1; cc++)
+#pragma unroll 1
+                for (int fi = 0; fi < 6; fi++)
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const float v = s_h1[cc][4 * a + fi][t + j];
+#pragma unroll
+                        for (int c2 = 0; c2 < SF_C2; c2++) acc[c2] += w2[((c2 * SF_C1 + cc) * 6 + fi) * 3 + j] * v;
+                    }
+        }
+        float ss = 0.f;
+#pragma unroll
+        for (int c2 = 0; c2 < SF_C2; c2++) ss += acc[c2] * acc[c2];
+        const float inv = rsqrtf(ss / (float)SF_C2 + eps);
+        const T* drow = dout + ((size_t)b * L + (inside ? l : 0)) * ldo;
+        float dot = 0.f;
+#pragma unroll
+        for (int c2 = 0; c2 < SF_C2; c2++) {
+            const float xh = acc[c2] * inv;
+            const float du = inside ? od_t<T>::ld(drow + c2 * SF_A2 + a) * od_silu_grad(xh * g2[c2]) : 0.f;
+            if (owned) s_r2[(c2 * SF_A2 + a) * SFB_TL + t - 1] = du * xh;
+            else if (t >= 1 && t <= SFB_TL) s_r2[(c2 * SF_A2 + a) * SFB_TL + t - 1] = 0.f;
+            acc[c2] = xh;
+            dot += du * g2[c2] * xh;
+            s_d2[c2][a][t] = du * g2[c2];                      // d x^, finished below
+        }
+        dot /= (float)SF_C2;
+#pragma unroll
+        for (int c2 = 0; c2 < SF_C2; c2++) s_d2[c2][a][t] = inv * (s_d2[c2][a][t] - acc[c2] * dot);
+    }
+    __syncthreads();
+    float* row = ws + ((size_t)b * gridDim.x + blockIdx.x) * SFB_COLS;
+    // conv2's weights: dw2[c2][cc][fi][j] = sum over the owned (a2, t) of dacc2[c2][a2][t] h1[cc][4 a2 + fi][t + j]
+    for (int i = tid; i < SFB_W2; i += 256) {
+        const int j = i % 3, fi = (i / 3) % 6, cc = (i / 18) % SF_C1, c2 = i / (18 * SF_C1);
+        float s = 0.f;
+        for (int a = 0; a < SF_A2; a++)
+            for (int t = 1; t <= SFB_TL; t++) s += s_d2[c2][a][t] * s_h1[cc][4 * a + fi][t + j];
+        row[SFB_W1 + 2 * SF_C1 + i] = s;
+    }
+    if (tid < 2 * SF_C2) {
+        const int c2 = tid % SF_C2;
+        float s = 0.f;
+        for (int a = 0; a < SF_A2; a++)
+            for (int t = 0; t < SFB_TL; t++) s += tid < SF_C2 ? s_d2[c2][a][t + 1] : s_r2[(c2 * SF_A2 + a) * SFB_TL + t];
+        row[SFB_W1 + 2 * SF_C1 + SFB_W2 + tid] = s;            // db2 then dg2
+    }
+    __syncthreads();
+    // gradient of the owned h1 positions (gathered from dacc2), through SiLU and the norm to conv1's output
+    for (int i = tid; i < SF_A1 * SFB_TL; i += 256) {
+        const int a1 = i / SFB_TL, t = i % SFB_TL, l = l0 + t;   // h1 row a1 + 1, column t + 2
+        float dh[SF_C1], acc[SF_C1];
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) { dh[cc] = 0.f; acc[cc] = b1[cc]; }
+        for (int a2 = 0; a2 < SF_A2; a2++) {
+            const int fi = a1 + 1 - 4 * a2;
+            if (fi < 0 || fi >= 6) continue;
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+#pragma unroll 4
+                for (int c2 = 0; c2 < SF_C2; c2++) {
+                    const float d = s_d2[c2][a2][t - j + 2];
+#pragma unroll
+                    for (int cc = 0; cc < SF_C1; cc++) dh[cc] += w2[((c2 * SF_C1 + cc) * 6 + fi) * 3 + j] * d;
+                }
+        }
+        for (int fi = 0; fi < 8; fi++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const float v = s_in[6 * a1 + fi][t + 2 + j];
+#pragma unroll
+                for (int cc = 0; cc < SF_C1; cc++) acc[cc] += w1[(cc * 8 + fi) * 3 + j] * v;
+            }
+        float ss = 0.f, dot = 0.f;
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) ss += acc[cc] * acc[cc];
+        const float inv = rsqrtf(ss / (float)SF_C1 + eps);
+        const bool inside = l < L;
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) {
+            const float xh = acc[cc] * inv;
+            const float du = inside ? dh[cc] * od_silu_grad(xh * g1[cc]) : 0.f;
+            acc[cc] = xh;
+            dh[cc] = du * g1[cc];
+            dot += dh[cc] * xh;
+            s_t1[(cc * SF_A1 + a1) * SFB_TL + t] = du * xh;
+        }
+        dot /= (float)SF_C1;
+#pragma unroll
+        for (int cc = 0; cc < SF_C1; cc++) s_r2[(cc * SF_A1 + a1) * SFB_TL + t] = inv * (dh[cc] - acc[cc] * dot);
+    }
+    __syncthreads();
+    // conv1's weights: dw1[cc][fi][j] = sum over the owned (a1, t) of dacc1[cc][a1][t] in[6 a1 + fi][t + 2 + j]
+    if (tid < SFB_W1) {
+        const int j = tid % 3, fi = (tid / 3) % 8, cc = tid / 24;
+        float s = 0.f;
+        for (int a = 0; a < SF_A1; a++)
+            for (int t = 0; t < SFB_TL; t++) s += s_r2[(cc * SF_A1 + a) * SFB_TL + t] * s_in[6 * a + fi][t + 2 + j];
+        row[tid] = s;
+    } else if (tid < SFB_W1 + 2 * SF_C1) {
+        const int k = tid - SFB_W1, cc = k % SF_C1;
+        const float* src = k < SF_C1 ? s_r2 : s_t1;
+        float s = 0.f;
+        for (int n = 0; n < SF_A1 * SFB_TL; n++) s += src[cc * SF_A1 * SFB_TL + n];
+        row[tid] = s;                                          // db1 then dg1
+    }
+}
+
+// y[i] += x[i]: where two branches' gradients of one activation meet (the chart encoder's h feeds the style head and the temporal layer)
+template <class T>
+__global__ __launch_bounds__(256) void add_rows_kernel(const T* __restrict__ x, T* __restrict__ y, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    float a[8], b[8];
+    od_ld8(x + i * 8, a);
+    od_ld8(y + i * 8, b);
+#pragma unroll
+    for (int e = 0; e < 8; e++) b[e] += a[e];
+    od_st8(y + i * 8, b);
+}
+
+}  // namespace
+
+extern "C" int od_latent_bwd_block_frames(int C) { return lanes_ok(C) ? bw_frames(C) : 0; }
+
+extern "C" int od_rmsnorm_affine_film_bwd(int dtype, const void* x, int ldx, const float* gamma, const float* ssg, const void* dy, int lddy,
+                                          void* dx, int lddx, int accumulate_dx, float* dgamma, float* dssg, float* ws, long ws_floats, int B,
+                                          int L, int C, float eps, int act, void* stream) {
+    if (!lanes_ok(C) || ldx % 8 || lddy % 8 || lddx % 8) return OD_ERR_ALIGN;
+    if (B <= 0 || L <= 0 || !dx || !dgamma || !ws || (ssg && !dssg)) return OD_ERR_ARG;
+    const int nbl = (int)bw_blocks(L, C);
+    if (ws_floats < (long)B * nbl * 3 * C) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((rms_affine_film_bwd_kernel<T_>), dim3(nbl, B), dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, gamma,
+                                ssg, (const T_*)dy, lddy, (T_*)dx, lddx, accumulate_dx, ws, L, C, eps, act));
+    launch_partial_sum((hipStream_t)stream, ws, 1, B * nbl, 3 * C, 0, dgamma, 0, C, C, 1, 0, 1.f);
+    if (ssg) launch_partial_sum((hipStream_t)stream, ws, B, nbl, 3 * C, C, dssg, 3 * C, 2 * C, 2 * C, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_rmsnorm_affine_gate_residual_bwd(int dtype, const void* h, int ldh, const float* gamma, const float* ssg, const void* dxo,
+                                                   int lddxo, void* dh, int lddh, float* dgamma, float* dssg, float* ws, long ws_floats,
+                                                   int B, int L, int C, float eps, void* stream) {
+    if (!lanes_ok(C) || ldh % 8 || lddxo % 8 || lddh % 8) return OD_ERR_ALIGN;
+    if (B <= 0 || L <= 0 || !dh || !dgamma || !ws || (ssg && !dssg)) return OD_ERR_ARG;
+    const int nbl = (int)bw_blocks(L, C);
+    if (ws_floats < (long)B * nbl * 2 * C) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((rms_affine_gate_res_bwd_kernel<T_>), dim3(nbl, B), dim3(256), 0, (hipStream_t)stream, (const T_*)h, ldh,
+                                gamma, ssg, (const T_*)dxo, lddxo, (T_*)dh, lddh, ws, L, C, eps));
+    launch_partial_sum((hipStream_t)stream, ws, 1, B * nbl, 2 * C, 0, dgamma, 0, C, C, 1, 0, 1.f);
+    if (ssg) launch_partial_sum((hipStream_t)stream, ws, B, nbl, 2 * C, C, dssg + 2 * C, 3 * C, C, C, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_unet_mixer_bwd(int dtype, const void* p, int ldp, int p_bcast, const void* gx, int ldg, const float* gamma,
+                                 const void* dxo, int lddxo, void* dp, int lddp, void* dgx, int lddg, float* dgamma, float* ws,
+                                 long ws_floats, int B, int L, int C, float eps, void* stream) {
+    if (!lanes_ok(C) || ldp % 8 || ldg % 8 || lddxo % 8 || lddp % 8 || lddg % 8) return OD_ERR_ALIGN;
+    if (B <= 0 || L <= 0 || !dp || !dgx || !dgamma || !ws) return OD_ERR_ARG;
+    const int nbl = (int)bw_blocks(L, C), rows = p_bcast ? nbl : B * nbl;
+    if (ws_floats < (long)rows * C) return OD_ERR_ARG;
+    if (p_bcast)
+        DISPATCH_T(dtype, OD_LAUNCH((mixer_bwd_kernel<T_, true>), dim3(nbl, 1), dim3(256), 0, (hipStream_t)stream, (const T_*)p, ldp,
+                                    (const T_*)gx, ldg, gamma, (const T_*)dxo, lddxo, dp, lddp, (T_*)dgx, lddg, ws, B, L, C, eps));
+    else
+        DISPATCH_T(dtype, OD_LAUNCH((mixer_bwd_kernel<T_, false>), dim3(nbl, B), dim3(256), 0, (hipStream_t)stream, (const T_*)p, ldp,
+                                    (const T_*)gx, ldg, gamma, (const T_*)dxo, lddxo, dp, lddp, (T_*)dgx, lddg, ws, B, L, C, eps));
+    launch_partial_sum((hipStream_t)stream, ws, 1, rows, C, 0, dgamma, 0, C, C, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_unet_down_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx, float* dw,
+                                float* db, float* ws, long ws_floats, int B, int Lo, int C, int stride, void* stream) {
+    if (!lanes_ok(C) || ldx % 8 || lddy % 8 || lddx % 8) return OD_ERR_ALIGN;
+    if (stride < 1 || stride > 8) return OD_ERR_UNSUPPORTED;
+    if (B <= 0 || Lo <= 0 || !dx || !dw || !db || !ws) return OD_ERR_ARG;
+    const int ks = 2 * (stride / 2) + 1;
+    const long My = (long)B * Lo, Mx = My * stride;
+    const int nb = (int)bw_blocks(My, C);
+    if (ws_floats < (long)nb * (ks + 1) * C) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((unet_down_bwd_dx_kernel<T_>), dim3(row_grid(Mx, C)), dim3(256), 0, (hipStream_t)stream, w, (const T_*)dy,
+                                lddy, (T_*)dx, lddx, B, Lo, C, stride));
+    DISPATCH_T(dtype, OD_LAUNCH((unet_resample_bwd_dw_kernel<T_, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx,
+                                (const T_*)dy, lddy, ws, B, Lo, C, stride));
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, (ks + 1) * C, 0, dw, 0, ks * C, C, ks, 1, 1.f / (float)stride);
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, (ks + 1) * C, ks * C, db, 0, C, C, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_unet_up_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx, float* dw,
+                              float* db, float* ws, long ws_floats, int B, int Li, int C, int stride, void* stream) {
+    if (!lanes_ok(C) || ldx % 8 || lddy % 8 || lddx % 8) return OD_ERR_ALIGN;
+    if (stride < 1 || stride > 8) return OD_ERR_UNSUPPORTED;
+    if (B <= 0 || Li <= 0 || !dx || !dw || !db || !ws) return OD_ERR_ARG;
+    const int ks = 2 * (stride / 2) + 1;
+    const long Mx = (long)B * Li, My = Mx * stride;
+    const int nb = (int)bw_blocks(My, C);
+    if (ws_floats < (long)nb * (ks + 1) * C) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((unet_up_bwd_dx_kernel<T_>), dim3(row_grid(Mx, C)), dim3(256), 0, (hipStream_t)stream, w, (const T_*)dy,
+                                lddy, (T_*)dx, lddx, B, Li, C, stride));
+    DISPATCH_T(dtype, OD_LAUNCH((unet_resample_bwd_dw_kernel<T_, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx,
+                                (const T_*)dy, lddy, ws, B, Li * stride, C, stride));
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, (ks + 1) * C, 0, dw, 0, ks * C, C, ks, 1, 1.f);
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, (ks + 1) * C, ks * C, db, 0, C, C, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_chart_head_bwd(int dtype, const void* x, int ldx, const float* W, const float* bias, const float* dout, void* dx, int lddx,
+                                 float* dW, float* db, float* ws, long ws_floats, int B, int L, int C, int N, int rms, float eps,
+                                 void* stream) {
+    if (!lanes_ok(C) || ldx % 8 || lddx % 8) return OD_ERR_ALIGN;
+    if (N < 1 || N > 16) return OD_ERR_UNSUPPORTED;
+    if (B <= 0 || L <= 0 || !dx || !dW || !db || !ws) return OD_ERR_ARG;
+    const long M = (long)B * L;
+    const int nb = (int)bw_blocks(M, C);
+    if (ws_floats < (long)nb * N * (C + 1)) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((chart_head_bwd_kernel<T_, 16>), dim3(nb), dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, W, bias, dout,
+                                (T_*)dx, lddx, ws, M, L, C, N, rms, eps));
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, N * (C + 1), 0, dW, 0, N * C, N * C, 1, 0, 1.f);
+    launch_partial_sum((hipStream_t)stream, ws, 1, nb, N * (C + 1), N * C, db, 0, N, N, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_attn_pool_bwd(int dtype, const void* scores, int lds, const void* values, int ldv, const float* dout, void* dscores,
+                                int ldds, void* dvalues, int lddv, int B, int L, int Hh, int hd, void* stream) {
+    if (hd < 8 || hd > 256 || (hd & (hd - 1)) || Hh < 1 || L < 1 || B < 1) return OD_ERR_UNSUPPORTED;
+    if (ldv % 8 || lddv % 8) return OD_ERR_ALIGN;
+    if (!dscores || !dvalues || !dout) return OD_ERR_ARG;
+    DISPATCH_T(dtype, OD_LAUNCH((attn_pool_bwd_kernel<T_>), dim3(Hh, B), dim3(256), 0, (hipStream_t)stream, (const T_*)scores, lds,
+                                (const T_*)values, ldv, dout, (T_*)dscores, ldds, (T_*)dvalues, lddv, L, Hh, hd));
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_proj_in_bwd_input(int dtype, const void* dx, int ldx, const float* W, float* dxt, int B, int E, int L, int D,
+                                    void* stream) {
+    if (E < 1 || E > 8) return OD_ERR_UNSUPPORTED;
+    if (!lanes_ok(D) || ldx % 8) return OD_ERR_ALIGN;
+    if (B <= 0 || L <= 0 || !dxt) return OD_ERR_ARG;
+    const long M = (long)B * L;
+    DISPATCH_T(dtype, OD_LAUNCH((proj_in_bwd_input_kernel<T_>), dim3(row_grid(M, D)), dim3(256), 0, (hipStream_t)stream, (const T_*)dx, ldx,
+                                W, dxt, M, L, D, E));
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_spec_features_conv_bwd(int dtype, const float* audio, const float* w1, const float* b1, const float* g1, const float* w2,
+                                         const float* b2, const float* g2, const void* dout, int ldo, float* dw1, float* db1, float* dg1,
+                                         float* dw2, float* db2, float* dg2, float* ws, long ws_floats, int B, int F, int L, float eps,
+                                         void* stream) {
+    if (F != SF_F) return OD_ERR_UNSUPPORTED;
+    if (B <= 0 || L <= 0 || !dw1 || !db1 || !dg1 || !dw2 || !db2 || !dg2 || !ws) return OD_ERR_ARG;
+    const int nbl = (L + SFB_TL - 1) / SFB_TL;
+    if (ws_floats < (long)B * nbl * SFB_COLS) return OD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, OD_LAUNCH((spec_conv_bwd_kernel<T_>), dim3(nbl, B), dim3(256), 0, st, audio, w1, b1, g1, w2, b2, g2, (const T_*)dout,
+                                ldo, ws, L, eps));
+    const int nb = B * nbl, o2 = SFB_W1 + 2 * SF_C1;
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, 0, dw1, 0, SFB_W1, SFB_W1, 1, 0, 1.f);
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, SFB_W1, db1, 0, SF_C1, SF_C1, 1, 0, 1.f);
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, SFB_W1 + SF_C1, dg1, 0, SF_C1, SF_C1, 1, 0, 1.f);
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, o2, dw2, 0, SFB_W2, SFB_W2, 1, 0, 1.f);
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, o2 + SFB_W2, db2, 0, SF_C2, SF_C2, 1, 0, 1.f);
+    launch_partial_sum(st, ws, 1, nb, SFB_COLS, o2 + SFB_W2 + SF_C2, dg2, 0, SF_C2, SF_C2, 1, 0, 1.f);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_add_rows(int dtype, const void* x, void* y, long n, void* stream) {
+    if (n <= 0 || !x || !y) return OD_ERR_ARG;
+    if (n % 8) return OD_ERR_ALIGN;
+    DISPATCH_T(dtype, OD_LAUNCH((add_rows_kernel<T_>), dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                (const T_*)x, (T_*)y, n / 8));
     OD_CHECK_LAUNCH();
     return 0;
 }

@@ -1,4 +1,4 @@
-"""`LatentModel` inference on the HIP path — the steps either side of `diffusion.sample` in `LDM.sample`
+"""`LatentModel` on the HIP path: inference — the steps either side of `diffusion.sample` in `LDM.sample`
 (osu_dreamer/models/inference/model.py:48,51; reference model: osu_dreamer/models/latent/model.py:38-134,
 unet.py:21-126, spec_features.py:10-32).
 
@@ -19,7 +19,20 @@ a common length, each keeps to its own frames, and every frame past a sequence's
 Activations are frame-major [B*L][h_dim] on the device; the tensors handed back are (B, C, L)-shaped *views* of
 those buffers (no transposing copy), and `decode` takes them back without one.  `encode_chart(chart) -> (z, s)`
 (chart encoder, style head, temporal head: the dataset-encoding direction of scripts/encode_latents.py) runs on
-the same kernels.  Training of the latent model is out of scope: parameters do not receive gradients here.
+the same kernels.
+
+Gradients (latent_grad.py).  Parameters are created with requires_grad = False, and with grad disabled or nothing requiring grad every
+call above takes the no-grad path, bit for bit as before.  After `model.requires_grad_(True)` (or when a `z`, `s` or skip input requires
+grad) `audio_encoder`, `encode_chart`, `decode_logits` and `forward` run as autograd Functions over the backward kernels of
+csrc/latent.hip: every parameter's `.grad` is filled, and gradients flow to `z` and `s` of `decode_logits` / `forward`, to the skips
+and `h` of `audio_encoder` (summed over the decoder rows when one audio row serves them all) and through the `z` and `s` that
+`encode_chart` returns, so the body of the reference's `LatentTrainer.forward` and any torch optimizer run on top of this model.  fp32 and
+`compute_dtype = torch.bfloat16` (bf16 activations and GEMM operands, fp32 accumulation and parameter gradients; the SpecFeatures front
+end up to its SiLU stays fp32 on the grad path, so in bf16 the training forward is not bit for bit the no-grad forward of the same
+model: the two differ by the bf16 rounding of that front end); `lengths=` and `f32_matmul = "bf16x3"` raise NotImplementedError with grad; `decode` stays no-grad.  Packed GEMM operands follow the parameters'
+version counters, so an optimizer's in-place step needs no `invalidate()`.  A graph is backpropagated once: a second backward through the
+same forward (retain_graph) raises, because the parameter gradients of a call are sums the kernels add into.  `LatentTrainer` / `fit-latent` (loss and MMD kernels,
+parameter arena, fused optimizer, graph capture) are not built.
 """
 from __future__ import annotations
 
@@ -31,7 +44,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from . import ops
+from . import latent_grad, ops
 from ._lib import OD_ACT_NONE, OD_ACT_SILU
 from .engine import Workspace
 
@@ -171,6 +184,8 @@ class LatentModel(nn.Module):
         self._ws: Dict[tuple, Workspace] = {}
         self._packed: Dict[str, torch.Tensor] = {}
         self._packed_key = None
+        self._packed_train = False
+        self._plist: Optional[List[nn.Parameter]] = None
         self._rowmap = None
         self.register_load_state_dict_post_hook(lambda m, k: m.invalidate())
 
@@ -192,7 +207,13 @@ class LatentModel(nn.Module):
 
     def invalidate(self):
         """Forget packed GEMM operands and workspaces (call after editing parameters in place)."""
-        self._packed, self._packed_key, self._ws = {}, None, {}
+        self._packed, self._packed_key, self._packed_train, self._ws, self._plist = {}, None, False, {}, None
+
+    def _params(self) -> List[nn.Parameter]:
+        """The parameters, listed once (the constructor registers them all; invalidate() forgets the list)."""
+        if self._plist is None:
+            self._plist = list(self.parameters())
+        return self._plist
 
     def P(self, name: str) -> torch.Tensor:
         return self.get_parameter(name)
@@ -211,12 +232,15 @@ class LatentModel(nn.Module):
         out += [(f"chart_encoder.1.layers.{i}.", False) for i in range(self.n_downs)]
         return out + [("style_head.0.", False), ("temporal_layer.", True)]
 
-    def _pack(self, dt: torch.dtype):
-        """fp32 parameters -> GEMM operands of the compute dtype; SwiGLU width padded hf -> hp (zero rows/cols)."""
+    def _pack(self, dt: torch.dtype, train: bool = False) -> Dict[str, torch.Tensor]:
+        """fp32 parameters -> GEMM operands of the compute dtype; SwiGLU width padded hf -> hp (zero rows/cols).  `train`: also the
+        transposed operands the backward's data GEMMs read (name + ".T").  Once the grad path has packed, the cache follows the parameters:
+        an optimizer edits them in place without calling invalidate(), which bumps their version counters, and those are then part of the
+        key.  A model that never took the grad path does not look at them (in-place edits need invalidate(), as before)."""
         dev = self.P("proj_out.weight").device
-        key = (dt, dev)
-        if self._packed_key == key:
-            return
+        key = (dt, dev, tuple(p._version for p in self._params()) if train or self._packed_train else None)
+        if self._packed_key == key and (self._packed_train or not train):
+            return self._packed
         pk: Dict[str, torch.Tensor] = {}
         hf, hp = self.hf, self.hp
         rm = [-1] * (2 * hp)
@@ -232,6 +256,11 @@ class LatentModel(nn.Module):
             if rmap is not None:
                 pk[name + ".b"] = torch.empty(Np, dtype=torch.float32, device=dev)
                 ops.pack_weight(self.P(name + ".bias"), pk[name + ".b"].view(Np, 1), row_map=rmap)
+            # (the chart takes no gradient; the grad path runs SpecFeatures' projection in fp32 on the parameter itself)
+            if train and name not in ("chart_encoder.0", "audio_encoder.0.net.8"):
+                # N < 8 (the pool's scores): the gradient rows are padded to one 8-wide k chunk, like the chart's 9 channels forward
+                pk[name + ".T"] = torch.empty(Kp or K, _ceil(Np or N, 8), dtype=dt, device=dev)
+                ops.pack_weight(w, pk[name + ".T"], transpose=True, row_map=rmap)
 
         pack("audio_encoder.0.net.8")
         pack("chart_encoder.0", Kp=16)                      # 9 chart channels, zero-padded to one 16-wide k chunk
@@ -244,7 +273,8 @@ class LatentModel(nn.Module):
         for i in range(self.n_downs):
             pack(f"decoder.mixers.{i}.proj.0")
             pack(f"decoder.mixers.{i}.gate")
-        self._packed, self._packed_key = pk, key
+        self._packed, self._packed_key, self._packed_train = pk, key, train
+        return pk
 
     def _workspace(self, tag: str, B: int, L: int, dt) -> Workspace:
         dev = self.P("proj_out.weight").device
@@ -315,8 +345,22 @@ class LatentModel(nn.Module):
         return out
 
     # ------------------------------------------------------------------ latent/model.py:54 (audio_encoder)
-    @torch.no_grad()
+    def _grad_path(self, *inputs) -> bool:
+        """Gradients are wanted: grad mode is on and a parameter (`model.requires_grad_(True)`) or one of `inputs` requires grad."""
+        return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in inputs) or
+                                            any(p.requires_grad for p in self._params()))
+
     def _audio_encoder(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None):
+        if not self._grad_path():                     # (the spectrogram itself takes no gradient)
+            return self._audio_encoder_nograd(audio, lengths)
+        if lengths is not None:
+            raise NotImplementedError("audio_encoder: `lengths=` (varlen) is an inference form; the grad path takes dense batches")
+        if audio.dim() != 3 or audio.shape[1] != A_DIM or audio.shape[2] % self.chunk_size:
+            raise ValueError(f"audio must be (B, {A_DIM}, L) with L a multiple of chunk_size {self.chunk_size}, got {tuple(audio.shape)}")
+        return latent_grad.audio_encoder(self, audio)
+
+    @torch.no_grad()
+    def _audio_encoder_nograd(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None):
         """`lengths` (one per row, multiples of chunk_size): row g of audio holds a song of lengths[g] frames, zero-padded to L; the skips
         and h are then 0 past each song's length at every level."""
         audio = audio.detach().to(torch.float32).contiguous()
@@ -376,7 +420,7 @@ class LatentModel(nn.Module):
         if skips is None:
             if audio is None:
                 raise ValueError("decode needs `audio` or `skips`")
-            skips, _ = self._audio_encoder(audio, lengths)
+            skips, _ = self._audio_encoder_nograd(audio, lengths)
         z = z.detach().to(torch.float32).contiguous()
         s = s.detach().to(torch.float32).contiguous()
         B, E, l = z.shape
@@ -437,7 +481,15 @@ class LatentModel(nn.Module):
         return out, s
 
     def decode_logits(self, z, s, *, audio=None, skips=None, lengths=None, offs=None) -> torch.Tensor:
-        return self._decode(z, s, audio, skips, n_sigmoid=0, lengths=lengths, offs=offs)[0]
+        if not self._grad_path(z, s, *(skips or ())):
+            return self._decode(z, s, audio, skips, n_sigmoid=0, lengths=lengths, offs=offs)[0]
+        if lengths is not None or offs is not None:
+            raise NotImplementedError("decode_logits: `lengths=` (varlen) is an inference form; the grad path takes dense batches")
+        if skips is None:
+            if audio is None:
+                raise ValueError("decode needs `audio` or `skips`")
+            skips, _ = self._audio_encoder(audio)
+        return latent_grad.decode_logits(self, z, s, skips)
 
     def _label_predictor(self, s: torch.Tensor) -> torch.Tensor:            # latent/model.py:72-76
         B = s.shape[0]
@@ -455,13 +507,24 @@ class LatentModel(nn.Module):
         chart, s32 = self._decode(z, s, audio, skips, n_sigmoid=N_HIT, lengths=lengths, offs=offs)
         return chart, self._label_predictor(s32).clamp_(0, 10)
 
-    @torch.no_grad()
     def forward(self, audio, z, s):                                          # latent/model.py:78-91
-        return self.decode_logits(z, s, audio=audio), self._label_predictor(s.detach().to(torch.float32).contiguous())
+        if self._grad_path(z, s):
+            return self.decode_logits(z, s, audio=audio), latent_grad.label_predictor(self, s)
+        with torch.no_grad():
+            return self.decode_logits(z, s, audio=audio), self._label_predictor(s.detach().to(torch.float32).contiguous())
 
     # ------------------------------------------------------------------ latent/model.py:93-101 (encode_chart)
-    @torch.no_grad()
     def encode_chart(self, chart: torch.Tensor, lengths: Optional[Sequence[int]] = None):
+        if not self._grad_path():                     # (the chart itself takes no gradient)
+            return self._encode_chart_nograd(chart, lengths)
+        if lengths is not None:
+            raise NotImplementedError("encode_chart: `lengths=` (varlen) is an inference form; the grad path takes dense batches")
+        if chart.dim() != 3 or chart.shape[1] != X_DIM or chart.shape[2] % self.chunk_size:
+            raise ValueError(f"chart must be (B, {X_DIM}, L) with L a multiple of chunk_size {self.chunk_size}, got {tuple(chart.shape)}")
+        return latent_grad.encode_chart(self, chart)
+
+    @torch.no_grad()
+    def _encode_chart_nograd(self, chart: torch.Tensor, lengths: Optional[Sequence[int]] = None):
         """chart (B, 9, L) -> z (B, emb_dim, L / chunk_size), s (B, style_dim): the dataset-encoding direction
         (scripts/encode_latents.py): chart encoder, style head (layer + AttnPool + rms_norm), temporal layer / head.
         `lengths` (one per map, multiples of chunk_size): map b holds lengths[b] frames; z is 0 past lengths[b] / chunk_size and s pools

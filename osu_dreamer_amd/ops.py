@@ -605,6 +605,107 @@ def attn_pool(scores, values, out, B, L, heads, hd):
                             _stream(scores))
 
 
+# ---------------------------------------------------------------- latent model, backward kernels.  Sums over frames (dgamma, dssg, dw,
+# db, dW) are fp32 and ADDED to their destination, in a fixed order: `ws` is fp32 scratch for the per-block partial rows, at least
+# latent_bwd_ws_floats(...) long.
+def latent_bwd_ws_floats(kind, B, L, C, n=0):
+    """Scratch floats of one backward call: kind 'film' / 'gate' / 'mixer' (n = 1: the skip is broadcast) with L the frames per batch
+    row; 'down' / 'up' with L the frames of dy per batch row and n the stride; 'head' with n the output channels; 'spec' (C unused)."""
+    if kind == "spec":
+        return B * -(-L // 32) * 4880
+    f = _lib.lib().cdll.od_latent_bwd_block_frames(C)
+    assert f > 0, "C must be a power of two in 8..512"
+    per_row, flat = -(-L // f), -(-(B * L) // f)
+    if kind == "film":
+        return B * per_row * 3 * C
+    if kind == "gate":
+        return B * per_row * 2 * C
+    if kind == "mixer":
+        return (per_row if n else B * per_row) * C
+    if kind in ("down", "up"):
+        return flat * (2 * (n // 2) + 2) * C
+    if kind == "head":
+        return flat * n * (C + 1)
+    raise ValueError(kind)
+
+
+def rmsnorm_affine_film_bwd(x, gamma, ssg, dy, dx, dgamma, dssg, ws, B, L, act=OD_ACT_NONE, accumulate_dx=False, eps=1e-6):
+    """dx (+)= ; dgamma += ; dssg[:, :2C] += (ssg None: dssg unused) — backward of rmsnorm_affine_film under dy."""
+    _f32(gamma, ssg, dgamma, dssg, ws)
+    assert x.dtype == dy.dtype == dx.dtype
+    _lib.lib().od_rmsnorm_affine_film_bwd(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(dy), _ld(dy), _p(dx), _ld(dx),
+                                          int(accumulate_dx), _p(dgamma), _p(dssg), _p(ws), ws.numel(), B, L, x.shape[1], eps, act,
+                                          _stream(x))
+
+
+def rmsnorm_affine_gate_residual_bwd(h, gamma, ssg, dxo, dh, dgamma, dssg, ws, B, L, eps=1e-6):
+    """dh ; dgamma += ; dssg[:, 2C:] += (ssg None: dssg unused) — backward of rmsnorm_affine_gate_residual under dxo (dx is dxo)."""
+    _f32(gamma, ssg, dgamma, dssg, ws)
+    assert h.dtype == dxo.dtype == dh.dtype
+    _lib.lib().od_rmsnorm_affine_gate_residual_bwd(dt_code(h.dtype), _p(h), _ld(h), _p(gamma), _p(ssg), _p(dxo), _ld(dxo), _p(dh),
+                                                   _ld(dh), _p(dgamma), _p(dssg), _p(ws), ws.numel(), B, L, h.shape[1], eps, _stream(h))
+
+
+def unet_mixer_bwd(p, p_bcast, gx, gamma, dxo, dp, dgx, dgamma, ws, B, L, eps=1e-6):
+    """dgx ; dgamma += ; dp: [B*L, C] of the activation type, or fp32 [L, C] summed over the batch when p_bcast (dx is dxo)."""
+    _f32(gamma, dgamma, ws)
+    assert p.dtype == gx.dtype == dxo.dtype == dgx.dtype and dp.dtype == (torch.float32 if p_bcast else p.dtype)
+    _lib.lib().od_unet_mixer_bwd(dt_code(p.dtype), _p(p), _ld(p), int(p_bcast), _p(gx), _ld(gx), _p(gamma), _p(dxo), _ld(dxo), _p(dp),
+                                 _ld(dp), _p(dgx), _ld(dgx), _p(dgamma), _p(ws), ws.numel(), B, L, p.shape[1], eps, _stream(p))
+
+
+def unet_down_bwd(x, w, dy, dx, dw, db, ws, B, Lo, stride):
+    _f32(w, dw, db, ws)
+    assert x.dtype == dy.dtype == dx.dtype
+    _lib.lib().od_unet_down_bwd(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(dy), _ld(dy), _p(dx), _ld(dx), _p(dw), _p(db), _p(ws),
+                                ws.numel(), B, Lo, x.shape[1], stride, _stream(x))
+
+
+def unet_up_bwd(x, w, dy, dx, dw, db, ws, B, Li, stride):
+    _f32(w, dw, db, ws)
+    assert x.dtype == dy.dtype == dx.dtype
+    _lib.lib().od_unet_up_bwd(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(dy), _ld(dy), _p(dx), _ld(dx), _p(dw), _p(db), _p(ws),
+                              ws.numel(), B, Li, x.shape[1], stride, _stream(x))
+
+
+def chart_head_bwd(x, W, bias, dout, dx, dW, db, ws, B, L, rms=False, eps=1e-6):
+    """dx ; dW += ; db += — backward of chart_head(n_sigmoid = 0) under dout (B, N, L) fp32."""
+    _f32(W, bias, dout, dW, db, ws)
+    N = W.shape[0]
+    assert tuple(dout.shape) == (B, N, L) and x.dtype == dx.dtype
+    _lib.lib().od_chart_head_bwd(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(dout), _p(dx), _ld(dx), _p(dW), _p(db), _p(ws),
+                                 ws.numel(), B, L, x.shape[1], N, int(rms), eps, _stream(x))
+
+
+def attn_pool_bwd(scores, values, dout, dscores, dvalues, B, L, heads, hd):
+    _f32(dout)
+    assert scores.dtype == values.dtype == dscores.dtype == dvalues.dtype
+    _lib.lib().od_attn_pool_bwd(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(dout), _p(dscores),
+                                _ld(dscores), _p(dvalues), _ld(dvalues), B, L, heads, hd, _stream(scores))
+
+
+def spec_features_conv_bwd(audio, w1, b1, g1, w2, b2, g2, dout, dw1, db1, dg1, dw2, db2, dg2, ws, eps=1e-6):
+    """dw1, db1, dg1, dw2, db2, dg2 += under dout [B*L, 96]; ws: at least latent_bwd_ws_floats('spec', B, L, 0) floats."""
+    B, F, L = audio.shape
+    _f32(audio, w1, b1, g1, w2, b2, g2, dw1, db1, dg1, dw2, db2, dg2, ws)
+    _lib.lib().od_spec_features_conv_bwd(dt_code(dout.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2), _p(dout),
+                                         _ld(dout), _p(dw1), _p(db1), _p(dg1), _p(dw2), _p(db2), _p(dg2), _p(ws), ws.numel(), B, F, L,
+                                         eps, _stream(audio))
+
+
+def add_rows(x, y):
+    """y += x (same dtype and shape, both contiguous)."""
+    assert x.dtype == y.dtype and x.shape == y.shape and x.is_contiguous() and y.is_contiguous()
+    _lib.lib().od_add_rows(dt_code(x.dtype), _p(x), _p(y), x.numel(), _stream(x))
+
+
+def proj_in_bwd_input(dx, W, dxt):
+    """dxt (B, E, L) fp32 = W^T dx: the gradient of proj_in's input."""
+    B, E, L = dxt.shape
+    _f32(W, dxt)
+    _lib.lib().od_proj_in_bwd_input(dt_code(dx.dtype), _p(dx), _ld(dx), _p(W), _p(dxt), B, E, L, dx.shape[1], _stream(dx))
+
+
 # ---------------------------------------------------------------- latent model, varlen forms (lens: device int32 [B], the valid
 # frames of each sequence at the level the call reads; frames past them come back as exact zeros)
 def _lens(lens, B):
