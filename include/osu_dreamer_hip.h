@@ -425,6 +425,47 @@ int od_add_rows(int dtype, const void* x, void* y, long n, void* stream);
  * replaces: autograd of latent/model.py:114 (proj_emb) towards z. */
 int od_proj_in_bwd_input(int dtype, const void* dx, int ldx, const float* W, float* dxt, int B, int E, int L, int D, void* stream);
 
+/* ---- training step of the latent model (latent/train.py:75-154): fp32 throughout; every sum over elements goes through per-block
+ *      partial rows in `ws` and a one-block second pass in row order, so two launches on the same input give the same bits ---- */
+/* out[0] = the unbiased MMD^2 of z [N][D] against prior [N][D] under the sum of seven inverse multiquadratic kernels C / (C + d^2),
+ * C = 2 D scale; out[1:4] = its zz, pp and zp terms; dz [N][D] = its gradient with respect to z.  Squared distances are sums of squared
+ * differences.  N >= 2, D <= 256; ws: 3 N floats.  replaces: common/wae.py:4-28 (mmd_imq) and its autograd, latent/train.py:88. */
+int od_mmd_imq(const float* z, const float* prior, float* out, float* dz, float* ws, long ws_floats, int N, int D, void* stream);
+/* y[n] = x[n] * g[0], g a device scalar: a stored gradient under the seed that backward() brings.
+ * replaces: autograd's scaling of the s_reg term, latent/train.py:146-149. */
+int od_scale_by(const float* x, const float* g, float* y, long n, void* stream);
+/* The decoder's inputs from z (B2, E, l; element strides zsb, zse, zsl) and s [B2][S]: s_out[b] = s[b ^ 1] (the other half's style);
+ * when training, + s_noise eps_s, z_out = z + z_noise eps_z, rows of s with u_s[b] < s_mask_frac replaced by repl[b] (masked[b] = 1, a
+ * byte per row), and frames [start, start + span) of row b of z zeroed, span = trunc((u_span[b] z_mask_frac) l), start =
+ * trunc(u_start[b] max(l - span, 1)), each product rounded to fp32 (start_span[b] = (start, span)).  A mask fraction <= 0 switches its
+ * mask off (its draws may be NULL).  z_out (B2, E, l) and s_out are contiguous.  replaces: latent/train.py:90-112. */
+int od_latent_perturb(const float* z, long zsb, long zse, long zsl, const float* s, const float* eps_z, const float* eps_s,
+                      const float* u_s, const float* repl, const float* u_span, const float* u_start, float* z_out, float* s_out,
+                      void* masked, void* start_span, int B2, int E, int l, int S, float s_noise, float z_noise, float s_mask_frac,
+                      float z_mask_frac, int training, void* stream);
+/* backward of od_latent_perturb: dz = dz_out outside the zeroed span, 0 inside; ds[b] = ds_out[b ^ 1], 0 where that row was replaced.
+ * replaces: autograd of latent/train.py:90-112. */
+int od_latent_perturb_bwd(const float* dz_out, const float* ds_out, const void* masked, const int* start_span, float* dz, float* ds,
+                          int B2, int E, int l, int S, void* stream);
+/* frames of one batch row a block of the loss kernels owns. */
+int od_latent_loss_block_frames(void);
+/* floats of `ws` for od_latent_loss. */
+int od_latent_loss_ws_floats(int B2, int L);
+/* The reconstruction loss of logits / chart (B2, 9, L), pred_labels / true_labels [B2][5] and masked (a byte per row): out[0:11] = the
+ * components (seven hit channels: BCE-with-logits minus the soft-target floor, mean over B2 L; cursor position, velocity, acceleration:
+ * mean square of the n-th difference of logits - chart on channels 7, 8; labels: per-row MSE summed over unmasked rows / max(count, 1)),
+ * out[11] = s_reg[0], out[12] = loss = sum_i w_i out[i] / max(loss_ema[i], 1e-8) + s_reg_weight s_reg[0].  When training, loss_ema is
+ * first updated on the device: copied if the byte ema_init[0] is 0 (then set to 1), else lerp(loss_ema, out, 0.01).  coef[0:11] = d loss /
+ * d (the argument of one term of component i).  L >= 3.  replaces: latent/train.py:115-149. */
+int od_latent_loss(const float* logits, const float* chart, const float* pred_labels, const float* true_labels, const void* masked,
+                   const float* s_reg, float* loss_ema, void* ema_init, float* out, float* coef, float* ws, long ws_floats, int B2, int L,
+                   float s_reg_weight, int training, void* stream);
+/* backward of od_latent_loss under the seed gradient g[0] (device scalar): dlogits (B2, 9, L), dlabels [B2][5] (0 on masked rows),
+ * ds_reg[0] = g[0] s_reg_weight.  replaces: autograd of latent/train.py:115-149. */
+int od_latent_loss_bwd(const float* logits, const float* chart, const float* pred_labels, const float* true_labels, const void* masked,
+                       const float* coef, const float* g, float* dlogits, float* dlabels, float* ds_reg, int B2, int L,
+                       float s_reg_weight, void* stream);
+
 /* ---- varlen forms of the latent kernels: G songs / maps stacked in the padded [B*L][C] layout; lens (device int32 [B]) = valid
  *      frames of sequence b at the level the call reads.  Taps and frames at or past lens[b] read as zero (selected, so padding may
  *      hold NaN) and frames there that the call writes come back as exact zeros.  Valid frames are bit for bit the plain call on

@@ -1354,3 +1354,415 @@ extern "C" int od_add_rows(int dtype, const void* x, void* y, long n, void* stre
     OD_CHECK_LAUNCH();
     return 0;
 }
+
+// ================================================================================================================================
+// Training-step kernels of LatentTrainer (latent/train.py:86-149): the WAE regulariser, the decoder-input perturbation and the
+// reconstruction loss with its gradient.  All fp32.  Sums over elements leave a block as one partial row and are added by one block in
+// row order (a fixed tree inside a block): no atomics, the same bits on every launch.
+// ================================================================================================================================
+namespace {
+
+constexpr int LL_T = 256;        // frames of one batch row a block of the loss kernels owns (one per thread)
+constexpr int LL_NS = 10;        // sums over frames: 7 hit channels, 3 cursor differences
+constexpr int LL_NL = 11;        // loss components: those and the label term
+constexpr int LL_HIT = 7;
+constexpr int MMD_DMAX = 256;
+
+// v[k][threadIdx.x] of every thread summed over the block, for k < n, in a fixed tree; the totals are s[k * 256]
+template <int NV>
+__device__ __forceinline__ void block_tree_sum(float (*s)[256]) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) s[k][threadIdx.x] += s[k][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- MMD with the sum of seven inverse multiquadratic kernels, common/wae.py:4-28 ------------------------------------------------
+// k(d2) = sum_s C_s / (C_s + d2), C_s = 2 D scale_s;  dk = dk / d(d2)
+__device__ __forceinline__ float imq7(float d2, float Cb, float& dk) {
+    const float sc[7] = {.1f, .2f, .5f, 1.f, 2.f, 5.f, 10.f};
+    float k = 0.f;
+    dk = 0.f;
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const float C = Cb * sc[i], inv = 1.f / (C + d2), r = C * inv;
+        k += r;
+        dk -= r * inv;
+    }
+    return k;
+}
+
+// Block i: row i of z and of p against every row j, squared distances by direct differences.  ws[i] = (sum_{j != i} k(z_i, z_j),
+// sum_{j != i} k(p_i, p_j), sum_j k(z_i, p_j));  dz[i] = the gradient of the value with respect to z_i.
+__global__ __launch_bounds__(256) void mmd_rows_kernel(const float* __restrict__ z, const float* __restrict__ p, float* __restrict__ ws,
+                                                       float* __restrict__ dz, int N, int D) {
+    __shared__ float s_zi[MMD_DMAX], s_pi[MMD_DMAX], s_cz[256], s_cp[256], s_red[3][256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (tid < D) {
+        s_zi[tid] = z[(size_t)i * D + tid];
+        s_pi[tid] = p[(size_t)i * D + tid];
+    }
+    __syncthreads();
+    const float Cb = 2.f * (float)D;
+    float a_zz = 0.f, a_pp = 0.f, a_zp = 0.f, gz = 0.f, gp = 0.f;
+    for (int j0 = 0; j0 < N; j0 += 256) {
+        const int j = j0 + tid;
+        float cz = 0.f, cp = 0.f;
+        if (j < N) {
+            float dzz = 0.f, dpp = 0.f, dzp = 0.f;
+            for (int d = 0; d < D; d++) {
+                const float zj = z[(size_t)j * D + d], pj = p[(size_t)j * D + d];
+                const float a = s_zi[d] - zj, b = s_pi[d] - pj, c = s_zi[d] - pj;
+                dzz += a * a;
+                dpp += b * b;
+                dzp += c * c;
+            }
+            a_zp += imq7(dzp, Cb, cp);
+            if (j != i) {
+                float unused;
+                a_zz += imq7(dzz, Cb, cz);
+                a_pp += imq7(dpp, Cb, unused);
+            }
+        }
+        s_cz[tid] = cz;
+        s_cp[tid] = cp;
+        __syncthreads();
+        if (tid < D) {
+            const int n = N - j0 < 256 ? N - j0 : 256;
+            for (int jj = 0; jj < n; jj++) {
+                gz += s_cz[jj] * (s_zi[tid] - z[(size_t)(j0 + jj) * D + tid]);
+                gp += s_cp[jj] * (s_zi[tid] - p[(size_t)(j0 + jj) * D + tid]);
+            }
+        }
+        __syncthreads();
+    }
+    // the pair (i, j) is in the zz sum twice; d(d2)/dz_i = 2 (z_i - .)
+    if (tid < D) dz[(size_t)i * D + tid] = 4.f / ((float)N * (float)(N - 1)) * gz - 4.f / ((float)N * (float)N) * gp;
+    s_red[0][tid] = a_zz;
+    s_red[1][tid] = a_pp;
+    s_red[2][tid] = a_zp;
+    block_tree_sum<3>(s_red);
+    if (tid < 3) ws[(size_t)i * 3 + tid] = s_red[tid][0];
+}
+
+// out = (value, zz, pp, zp): the N partial rows added in row order
+__global__ __launch_bounds__(256) void mmd_finalize_kernel(const float* __restrict__ ws, float* __restrict__ out, int N) {
+    __shared__ float s_red[3][256];
+    const int tid = threadIdx.x;
+    float a[3] = {0.f, 0.f, 0.f};
+    for (int r = tid; r < N; r += 256)
+        for (int k = 0; k < 3; k++) a[k] += ws[(size_t)r * 3 + k];
+    for (int k = 0; k < 3; k++) s_red[k][tid] = a[k];
+    block_tree_sum<3>(s_red);
+    if (tid == 0) {
+        const float n = (float)N, zz = s_red[0][0] / (n * (n - 1.f)), pp = s_red[1][0] / (n * (n - 1.f)), zp = s_red[2][0] / (n * n);
+        out[0] = zz + pp - 2.f * zp;
+        out[1] = zz;
+        out[2] = pp;
+        out[3] = zp;
+    }
+}
+
+__global__ __launch_bounds__(256) void scale_by_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ y, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = x[i] * g[0];
+}
+
+// ---- perturbation of the decoder's inputs, latent/train.py:90-112 -------------------------------------------------------------
+// span and start of a row's zeroed frames, in the reference's operation order: every product is rounded to fp32 on its own
+__device__ __forceinline__ void mask_span(float u_span, float u_start, float frac, int l, int& start, int& span) {
+#pragma clang fp contract(off)
+    const float a = u_span * frac;
+    span = (int)(a * (float)l);
+    const int room = l - span > 1 ? l - span : 1;
+    start = (int)(u_start * (float)room);
+}
+
+__device__ __forceinline__ float add_scaled(float x, float w, float e) {
+#pragma clang fp contract(off)
+    const float t = w * e;
+    return x + t;
+}
+
+__global__ __launch_bounds__(256) void latent_perturb_kernel(const float* __restrict__ z, long zsb, long zse, long zsl,
+                                                             const float* __restrict__ s, const float* __restrict__ eps_z,
+                                                             const float* __restrict__ eps_s, const float* __restrict__ u_s,
+                                                             const float* __restrict__ repl, const float* __restrict__ u_span,
+                                                             const float* __restrict__ u_start, float* __restrict__ z_out,
+                                                             float* __restrict__ s_out, unsigned char* __restrict__ masked,
+                                                             int* __restrict__ start_span, int B2, int E, int l, int S, float s_noise,
+                                                             float z_noise, float s_frac, float z_frac, int training) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, nz = (long)B2 * E * l;
+    if (i < nz) {
+        const int b = (int)(i / ((long)E * l)), r = (int)(i % ((long)E * l)), e = r / l, t = r % l;
+        float v = z[b * zsb + e * zse + t * zsl];
+        int st = 0, sp = 0;
+        if (training) {
+            v = add_scaled(v, z_noise, eps_z[i]);
+            if (z_frac > 0.f) {
+                mask_span(u_span[b], u_start[b], z_frac, l, st, sp);
+                if (t >= st && t < st + sp) v = 0.f;
+            }
+        }
+        z_out[i] = v;
+        if (r == 0) {
+            start_span[2 * b] = st;
+            start_span[2 * b + 1] = sp;
+        }
+    } else if (i < nz + (long)B2 * S) {
+        const long j = i - nz;
+        const int b = (int)(j / S), c = (int)(j % S);
+        float v = s[(size_t)(b ^ 1) * S + c];          // each half is decoded with the other half's style
+        int m = 0;
+        if (training) {
+            v = add_scaled(v, s_noise, eps_s[j]);
+            if (s_frac > 0.f) {
+                m = u_s[b] < s_frac;
+                if (m) v = repl[j];
+            }
+        }
+        s_out[j] = v;
+        if (c == 0) masked[b] = (unsigned char)m;
+    }
+}
+
+__global__ __launch_bounds__(256) void latent_perturb_bwd_kernel(const float* __restrict__ dz_out, const float* __restrict__ ds_out,
+                                                                 const unsigned char* __restrict__ masked,
+                                                                 const int* __restrict__ start_span, float* __restrict__ dz,
+                                                                 float* __restrict__ ds, int B2, int E, int l, int S) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, nz = (long)B2 * E * l;
+    if (i < nz) {
+        const int b = (int)(i / ((long)E * l)), t = (int)(i % l);
+        const int st = start_span[2 * b], sp = start_span[2 * b + 1];
+        dz[i] = (t >= st && t < st + sp) ? 0.f : dz_out[i];
+    } else if (i < nz + (long)B2 * S) {
+        const long j = i - nz;
+        const int b = (int)(j / S), c = (int)(j % S), o = b ^ 1;       // s[b] went to row o
+        ds[j] = masked[o] ? 0.f : ds_out[(size_t)o * S + c];
+    }
+}
+
+// ---- reconstruction loss, latent/train.py:115-149 ------------------------------------------------------------------------------
+__device__ __forceinline__ float xlogx(float t) { return t > 0.f ? t * logf(t) : 0.f; }
+
+// Block (tile, b): LL_T frames of row b.  Partial row: the LL_NS sums of the tile (cursor differences that start in it).
+__global__ __launch_bounds__(256) void latent_loss_sums_kernel(const float* __restrict__ logits, const float* __restrict__ chart,
+                                                               float* __restrict__ ws, int L) {
+    __shared__ float s_red[LL_NS][256];
+    const int tid = threadIdx.x, b = blockIdx.y, l = blockIdx.x * LL_T + tid;
+    const float* x = logits + (size_t)b * 9 * L;
+    const float* y = chart + (size_t)b * 9 * L;
+    float acc[LL_NS];
+#pragma unroll
+    for (int k = 0; k < LL_NS; k++) acc[k] = 0.f;
+    if (l < L) {
+#pragma unroll
+        for (int k = 0; k < LL_HIT; k++) {
+            const float v = x[(size_t)k * L + l], t = y[(size_t)k * L + l];
+            const float bce = fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
+            acc[k] = bce + (xlogx(t) + xlogx(1.f - t));         // minus the soft-target floor -t log t - (1 - t) log(1 - t)
+        }
+        for (int c = LL_HIT; c < 9; c++) {
+            const float* xe = x + (size_t)c * L;
+            const float* ye = y + (size_t)c * L;
+            const float e0 = xe[l] - ye[l];
+            acc[7] += e0 * e0;
+            if (l + 1 < L) {
+                const float e1 = xe[l + 1] - ye[l + 1], d1 = e1 - e0;
+                acc[8] += d1 * d1;
+                if (l + 2 < L) {
+                    const float e2 = xe[l + 2] - ye[l + 2], d2 = (e2 - e1) - d1;
+                    acc[9] += d2 * d2;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < LL_NS; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<LL_NS>(s_red);
+    if (tid < LL_NS) ws[((size_t)b * gridDim.x + blockIdx.x) * LL_NS + tid] = s_red[tid][0];
+}
+
+// One block: the partial rows added in row order, the label term, the EMA of the components, the weighted loss, the 13 logged values
+// (the 11 components, s_reg, loss) and the 11 gradient coefficients d loss / d (one term of component i).
+__global__ __launch_bounds__(256) void latent_loss_finalize_kernel(const float* __restrict__ ws, int nrows, const float* __restrict__ pred_labels,
+                                                                   const float* __restrict__ true_labels,
+                                                                   const unsigned char* __restrict__ masked, const float* __restrict__ s_reg,
+                                                                   float* __restrict__ loss_ema, unsigned char* __restrict__ ema_init,
+                                                                   float* __restrict__ out, float* __restrict__ coef, int B2, int L,
+                                                                   float s_reg_weight, int training) {
+    __shared__ float s_red[LL_NS + 2][256];
+    const int tid = threadIdx.x;
+    float acc[LL_NS + 2];
+#pragma unroll
+    for (int k = 0; k < LL_NS + 2; k++) acc[k] = 0.f;
+    for (int r = tid; r < nrows; r += 256)
+#pragma unroll
+        for (int k = 0; k < LL_NS; k++) acc[k] += ws[(size_t)r * LL_NS + k];
+    for (int b = tid; b < B2; b += 256)
+        if (!masked[b]) {
+            float q = 0.f;
+            for (int j = 0; j < 5; j++) {
+                const float d = pred_labels[b * 5 + j] - true_labels[b * 5 + j];
+                q += d * d;
+            }
+            acc[LL_NS] += q / 5.f;
+            acc[LL_NS + 1] += 1.f;
+        }
+#pragma unroll
+    for (int k = 0; k < LL_NS + 2; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<LL_NS + 2>(s_red);
+    if (tid == 0) {
+        const float wts[LL_NL] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 2.f, 2.f, 2.f, 2.f};      // LOSS_COMPONENT_WEIGHTS, train.py:21-33
+        float n[LL_NL], g[LL_NL];      // component i = (its sum) / n[i];  d (its sum) / d (a term's argument) carries g[i]
+        for (int k = 0; k < LL_HIT; k++) { n[k] = (float)B2 * (float)L; g[k] = 1.f; }
+        for (int k = 0; k < 3; k++) { n[LL_HIT + k] = (float)B2 * 2.f * (float)(L - k); g[LL_HIT + k] = 2.f; }
+        n[10] = fmaxf(s_red[LL_NS + 1][0], 1.f);
+        g[10] = 2.f / 5.f;
+        const int first = training && !ema_init[0];
+        float loss = 0.f;
+        for (int k = 0; k < LL_NL; k++) {
+            const float v = s_red[k][0] / n[k];
+            float ema = loss_ema[k];
+            if (training) {
+                ema = first ? v : ema + 0.01f * (v - ema);
+                loss_ema[k] = ema;
+            }
+            const float c = wts[k] / fmaxf(ema, 1e-8f);
+            loss += c * v;
+            out[k] = v;
+            coef[k] = c * g[k] / n[k];
+        }
+        if (first) ema_init[0] = 1;
+        out[LL_NL] = s_reg[0];
+        out[LL_NL + 1] = loss + s_reg_weight * s_reg[0];
+    }
+}
+
+// Block (tile, b): dlogits of LL_T frames of row b under the seed gradient g[0]; the cursor rows read two frames of halo on each side
+// from global memory.  Tile 0 also writes the row's dlabels, block (0, 0) the gradient of s_reg.
+__global__ __launch_bounds__(256) void latent_loss_grad_kernel(const float* __restrict__ logits, const float* __restrict__ chart,
+                                                               const float* __restrict__ pred_labels, const float* __restrict__ true_labels,
+                                                               const unsigned char* __restrict__ masked, const float* __restrict__ coef,
+                                                               const float* __restrict__ g, float* __restrict__ dlogits,
+                                                               float* __restrict__ dlabels, float* __restrict__ ds_reg, int L,
+                                                               float s_reg_weight) {
+    const int tid = threadIdx.x, b = blockIdx.y, l = blockIdx.x * LL_T + tid;
+    const float seed = g[0];
+    if (blockIdx.x == 0) {
+        if (tid < 5) dlabels[b * 5 + tid] = masked[b] ? 0.f : seed * coef[10] * (pred_labels[b * 5 + tid] - true_labels[b * 5 + tid]);
+        if (b == 0 && tid == 5) ds_reg[0] = seed * s_reg_weight;
+    }
+    if (l >= L) return;
+    const float* x = logits + (size_t)b * 9 * L;
+    const float* y = chart + (size_t)b * 9 * L;
+    float* dx = dlogits + (size_t)b * 9 * L;
+#pragma unroll
+    for (int k = 0; k < LL_HIT; k++) {
+        const float v = x[(size_t)k * L + l], t = y[(size_t)k * L + l];
+        const float ev = expf(-fabsf(v)), sg = (v >= 0.f ? 1.f : ev) / (1.f + ev);
+        dx[(size_t)k * L + l] = seed * coef[k] * (sg - t);
+    }
+    const float c0 = coef[7], c1 = coef[8], c2 = coef[9];
+    for (int c = LL_HIT; c < 9; c++) {
+        const float* xe = x + (size_t)c * L;
+        const float* ye = y + (size_t)c * L;
+        float e[5];                                         // e[l - 2 .. l + 2], 0 outside the row (never used there)
+#pragma unroll
+        for (int o = 0; o < 5; o++) {
+            const int m = l + o - 2;
+            e[o] = (m >= 0 && m < L) ? xe[m] - ye[m] : 0.f;
+        }
+        float gr = c0 * e[2];
+        // first differences d1[j] = e[j + 1] - e[j], j <= L - 2: frame l is the +1 end of d1[l - 1] and the -1 end of d1[l]
+        float a1 = 0.f;
+        if (l >= 1) a1 += e[2] - e[1];
+        if (l + 1 < L) a1 -= e[3] - e[2];
+        gr += c1 * a1;
+        // second differences d2[j] = e[j + 2] - 2 e[j + 1] + e[j], j <= L - 3
+        float a2 = 0.f;
+        if (l >= 2) a2 += (e[2] - e[1]) - (e[1] - e[0]);
+        if (l >= 1 && l + 1 < L) a2 -= 2.f * ((e[3] - e[2]) - (e[2] - e[1]));
+        if (l + 2 < L) a2 += (e[4] - e[3]) - (e[3] - e[2]);
+        gr += c2 * a2;
+        dx[(size_t)c * L + l] = seed * gr;
+    }
+}
+
+}  // namespace
+
+extern "C" int od_latent_loss_block_frames(void) { return LL_T; }
+
+extern "C" int od_latent_loss_ws_floats(int B2, int L) { return B2 * ((L + LL_T - 1) / LL_T) * LL_NS; }
+
+extern "C" int od_mmd_imq(const float* z, const float* prior, float* out, float* dz, float* ws, long ws_floats, int N, int D, void* stream) {
+    if (N < 2 || D < 1 || D > MMD_DMAX) return OD_ERR_UNSUPPORTED;
+    if (!z || !prior || !out || !dz || !ws || ws_floats < (long)N * 3) return OD_ERR_ARG;
+    OD_LAUNCH(mmd_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, z, prior, ws, dz, N, D);
+    OD_LAUNCH(mmd_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, out, N);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_scale_by(const float* x, const float* g, float* y, long n, void* stream) {
+    if (n <= 0 || !x || !g || !y) return OD_ERR_ARG;
+    OD_LAUNCH(scale_by_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, g, y, n);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_perturb(const float* z, long zsb, long zse, long zsl, const float* s, const float* eps_z, const float* eps_s,
+                                 const float* u_s, const float* repl, const float* u_span, const float* u_start, float* z_out,
+                                 float* s_out, void* masked, void* start_span, int B2, int E, int l, int S, float s_noise, float z_noise,
+                                 float s_mask_frac, float z_mask_frac, int training, void* stream) {
+    if (B2 <= 0 || B2 % 2 || E <= 0 || l <= 0 || S <= 0 || !z || !s || !z_out || !s_out || !masked || !start_span) return OD_ERR_ARG;
+    if (training && (!eps_z || !eps_s || (s_mask_frac > 0.f && (!u_s || !repl)) || (z_mask_frac > 0.f && (!u_span || !u_start))))
+        return OD_ERR_ARG;
+    const long n = (long)B2 * E * l + (long)B2 * S;
+    OD_LAUNCH(latent_perturb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, zsb, zse, zsl, s, eps_z,
+              eps_s, u_s, repl, u_span, u_start, z_out, s_out, (unsigned char*)masked, (int*)start_span, B2, E, l, S, s_noise, z_noise,
+              s_mask_frac, z_mask_frac, training);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_perturb_bwd(const float* dz_out, const float* ds_out, const void* masked, const int* start_span, float* dz,
+                                     float* ds, int B2, int E, int l, int S, void* stream) {
+    if (B2 <= 0 || B2 % 2 || E <= 0 || l <= 0 || S <= 0 || !dz_out || !ds_out || !masked || !start_span || !dz || !ds) return OD_ERR_ARG;
+    const long n = (long)B2 * E * l + (long)B2 * S;
+    OD_LAUNCH(latent_perturb_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dz_out, ds_out,
+              (const unsigned char*)masked, start_span, dz, ds, B2, E, l, S);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_loss(const float* logits, const float* chart, const float* pred_labels, const float* true_labels,
+                              const void* masked, const float* s_reg, float* loss_ema, void* ema_init, float* out, float* coef, float* ws,
+                              long ws_floats, int B2, int L, float s_reg_weight, int training, void* stream) {
+    if (L < 3) return OD_ERR_UNSUPPORTED;                  // the second difference needs three frames
+    if (B2 <= 0 || !logits || !chart || !pred_labels || !true_labels || !masked || !s_reg || !loss_ema || !ema_init || !out || !coef || !ws)
+        return OD_ERR_ARG;
+    const int nbl = (L + LL_T - 1) / LL_T;
+    if (ws_floats < (long)B2 * nbl * LL_NS) return OD_ERR_ARG;
+    OD_LAUNCH(latent_loss_sums_kernel, dim3(nbl, B2), dim3(256), 0, (hipStream_t)stream, logits, chart, ws, L);
+    OD_LAUNCH(latent_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, B2 * nbl, pred_labels, true_labels,
+              (const unsigned char*)masked, s_reg, loss_ema, (unsigned char*)ema_init, out, coef, B2, L, s_reg_weight, training);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_loss_bwd(const float* logits, const float* chart, const float* pred_labels, const float* true_labels,
+                                  const void* masked, const float* coef, const float* g, float* dlogits, float* dlabels, float* ds_reg,
+                                  int B2, int L, float s_reg_weight, void* stream) {
+    if (L < 3) return OD_ERR_UNSUPPORTED;
+    if (B2 <= 0 || !logits || !chart || !pred_labels || !true_labels || !masked || !coef || !g || !dlogits || !dlabels || !ds_reg)
+        return OD_ERR_ARG;
+    OD_LAUNCH(latent_loss_grad_kernel, dim3((L + LL_T - 1) / LL_T, B2), dim3(256), 0, (hipStream_t)stream, logits, chart, pred_labels,
+              true_labels, (const unsigned char*)masked, coef, g, dlogits, dlabels, ds_reg, L, s_reg_weight);
+    OD_CHECK_LAUNCH();
+    return 0;
+}

@@ -197,3 +197,102 @@ def write_synthetic_dataset(data_path: str, n_maps: int = 8, frames=4096, a_dim:
         s /= np.sqrt((s * s).mean() + 1e-6)
         np.save(d / "h.npy", rng.standard_normal((a_dim, frames)).astype(np.float32))
         np.savez(d / "0.latent.npz", z=z, s=s, labels=(rng.random(NUM_LABELS) * 10).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------- latent-model feeder
+A_DIM, X_DIM = 72, 9
+CURSOR_X, CURSOR_Y = 7, 8              # data/beatmap/encode.py: BeatmapEncoding.X, .Y
+
+
+class Batch(NamedTuple):
+    audio: torch.Tensor    # (A_DIM, L) spectrogram
+    chart: torch.Tensor    # (X_DIM, L) encoded beatmap
+    labels: torch.Tensor   # (NUM_LABELS,)
+
+
+class BeatmapDataset(IterableDataset):
+    """`<mapset>/spec.npy` + `<mapset>/<map>.map.npy` -> `Batch`es (data/modules/beatmap.py:119-207).  seq_len None: whole maps (validation);
+    otherwise `seq_len` windows from a random start offset, at most `max_per_map` of them per map in random order, each with the x / y flip
+    augmentation (v <- 1 - v on a cursor channel, with probability 1/2 each).  Files are sharded by (rank, worker), as LatentDataset's."""
+
+    def __init__(self, mapsets: List[Path], seq_len: Optional[int] = None, shuffle_buffer_size: int = 1, max_per_map: int = -1,
+                 rank: int = 0, world_size: int = 1):
+        super().__init__()
+        self.mapsets, self.seq_len = mapsets, seq_len
+        self.shuffle_buffer_size = shuffle_buffer_size
+        self.max_per_map = max_per_map if max_per_map > 0 else float("inf")
+        self.rank, self.world_size = rank, world_size
+
+    def _files(self) -> Iterator[Path]:
+        return (f for m in self.mapsets for f in sorted(m.glob("*.map.npy")))
+
+    def _stream(self, nshards: int, shard: int) -> Iterator[Batch]:
+        for i, f in enumerate(self._files()):
+            if i % nshards == shard:
+                yield from self.make_samples(f)
+
+    __iter__ = LatentDataset.__iter__          # seeding, (rank, worker) shard and shuffle buffer are the latent feeder's
+
+    def make_samples(self, map_file: Path) -> Iterator[Batch]:
+        audio = torch.from_numpy(read_spec(map_file.parent / "spec.npy")).float()
+        chart_arr, label_arr = read_beatmap(map_file)
+        chart, labels = torch.from_numpy(chart_arr).float(), torch.from_numpy(np.asarray(label_arr)).float()
+        if self.seq_len is None:
+            yield Batch(audio, chart, labels)
+            return
+        end = chart.size(-1) - self.seq_len + 1
+        if end < 1:
+            return
+        start = int(torch.randint(0, min(self.seq_len, end), ()).item())
+        idxs = torch.arange(start, end, self.seq_len)
+        idxs = idxs[torch.randperm(len(idxs))[: int(min(self.max_per_map, len(idxs)))]]
+        for i in idxs:
+            window = chart[..., i:i + self.seq_len].clone()
+            if torch.rand(()) < 0.5:
+                window[CURSOR_X].mul_(-1).add_(1)
+            if torch.rand(()) < 0.5:
+                window[CURSOR_Y].mul_(-1).add_(1)
+            yield Batch(audio[..., i:i + self.seq_len].clone(), window, labels)       # cloned: the buffer must not pin the whole spectrogram
+
+
+class BeatmapDataModule:
+    """Same constructor keys as the reference's BeatmapDataModule (the YAML `data:` block of fit-latent)."""
+
+    def __init__(self, batch_size: int, seq_len: int, num_workers: int, max_val_count: int = 512, max_val_frac: float = .3,
+                 data_path: str = "./data", shuffle_buffer_size: int = 1, max_per_map: int = -1, rank: int = 0, world_size: int = 1):
+        self.batch_size, self.seq_len, self.num_workers = batch_size, seq_len, num_workers
+        train, val = hold_out_mapsets(Path(data_path), "*.map.npy", max_val_count, max_val_frac)
+        self.train_set = BeatmapDataset(train, seq_len, shuffle_buffer_size, max_per_map, rank, world_size)
+        self.val_set = BeatmapDataset(val)
+
+    def train_dataloader(self):
+        return DataLoader(self.train_set, batch_size=self.batch_size, num_workers=self.num_workers, pin_memory=True,
+                          persistent_workers=self.num_workers > 0, drop_last=True)
+
+    def val_dataloader(self):
+        return DataLoader(self.val_set, batch_size=1, num_workers=min(1, self.num_workers), pin_memory=True,
+                          persistent_workers=self.num_workers > 0)
+
+
+def write_synthetic_beatmaps(data_path: str, n_mapsets: int = 8, maps_per_set: int = 2, frames=4096, seed: int = 0):
+    """`n_mapsets` mapset dirs each with spec.npy (uint8 (A_DIM, frames)) and `maps_per_set` files `<n>.map.npy` in the format read_beatmap
+    reads (an npz: hit uint8 (7, L), xy uint16 (2, L), xy_min, xy_rng, labels), from seeded noise.  `frames` may be a list (one length
+    per mapset)."""
+    rng = np.random.default_rng(seed)
+    root = Path(data_path)
+    lengths = list(frames) if isinstance(frames, (list, tuple)) else [frames] * n_mapsets
+    for i in range(n_mapsets):
+        d = root / f"{i:04d}"
+        d.mkdir(parents=True, exist_ok=True)
+        L = lengths[i]
+        np.save(d / "spec.npy", rng.integers(0, 256, (A_DIM, L), dtype=np.uint8))
+        for n in range(maps_per_set):
+            hit = rng.random((X_DIM - 2, L))
+            hit[rng.random(hit.shape) < 0.5] = 0.0
+            xy = np.cumsum(rng.standard_normal((2, L)) * 8, axis=1) + np.array([[256.], [192.]])
+            xy_min = xy.min(axis=1, keepdims=True)
+            xy_rng = xy.max(axis=1, keepdims=True) - xy_min
+            xy_rng[xy_rng == 0.] = 1.
+            with open(d / f"{n}.map.npy", "wb") as f:
+                np.savez(f, hit=np.round(hit * 255).astype(np.uint8), xy=np.round((xy - xy_min) / xy_rng * 65535).astype(np.uint16),
+                         xy_min=xy_min, xy_rng=xy_rng, labels=rng.random(NUM_LABELS) * 10)

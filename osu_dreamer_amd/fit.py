@@ -1,4 +1,4 @@
-"""`fit-denoiser` / `fit-style` — the training shell around `DiffusionTrainer` and `StyleTrainer`.
+"""`fit-denoiser` / `fit-style` / `fit-latent` — the training shell around `DiffusionTrainer`, `StyleTrainer` and `LatentTrainer`.
 
 The reference drives its LightningModule with `LightningCLI` + `pytorch_lightning.Trainer`
 (osu_dreamer/scripts/fit_denoiser.py:17-32) configured by models/diffusion/model.yml:3-40.
@@ -18,6 +18,9 @@ reads them unchanged.
 `fit-style` (osu_dreamer/scripts/fit_style.py, models/style/model.yml) drives `StyleTrainer` through the same shell: the checkpoint
 monitor is `val/energy_dist` (mode min), and validation goes through the module's epoch hooks (on_validation_epoch_start /
 validation_step / on_validation_epoch_end), which log every value themselves.  It trains on one device, as the reference does.
+
+`fit-latent` (osu_dreamer/scripts/fit_latent.py, models/latent/model.yml) drives `LatentTrainer` the same way over `BeatmapDataModule`:
+ModelCheckpoint and EarlyStopping on `eval/score` with mode max (`monitor_mode`, `early_stop_patience`, `early_stop_min_delta`), one device.
 """
 from __future__ import annotations
 
@@ -41,6 +44,7 @@ from .train import DiffusionTrainer
 
 DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "model.yml")
 DEFAULT_STYLE_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "style.yml")
+DEFAULT_LATENT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "latent.yml")
 
 
 def seed_everything(seed) -> int:
@@ -64,7 +68,8 @@ class Trainer:
                  gradient_clip_val: Optional[float] = None, log_every_n_steps: int = 5,
                  val_check_interval: Optional[int] = None, limit_val_batches: Optional[int] = None,
                  default_root_dir: str = "runs/denoiser", accelerator: str = "gpu", devices: int = 1,
-                 enable_checkpointing: bool = True, monitor: str = "val/loss", **_ignored):
+                 enable_checkpointing: bool = True, monitor: str = "val/loss", monitor_mode: str = "min",
+                 early_stop_patience: Optional[int] = None, early_stop_min_delta: Optional[float] = None, **_ignored):
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.precision = str(precision)
         self.gradient_clip_val = gradient_clip_val
@@ -73,9 +78,18 @@ class Trainer:
         self.limit_val_batches = limit_val_batches
         self.root = default_root_dir
         self.enable_checkpointing = enable_checkpointing
-        self.monitor = monitor                        # ModelCheckpoint(monitor=..., mode=min, save_top_k=1)
+        self.monitor = monitor                        # ModelCheckpoint(monitor=..., mode=monitor_mode, save_top_k=1)
+        if monitor_mode not in ("min", "max"):
+            raise ValueError(f"monitor_mode must be 'min' or 'max', got {monitor_mode!r}")
+        self.monitor_mode = monitor_mode
+        self._worst = float("inf") if monitor_mode == "min" else float("-inf")
         self.global_step, self.epoch = 0, 0
-        self.best_val = float("inf")
+        self.best_val = self._worst
+        # EarlyStopping(monitor=..., mode=monitor_mode, patience, min_delta): stop after `patience` validations in a row that did not
+        # improve on the best one by more than min_delta
+        self.early_stop_patience = early_stop_patience
+        self.early_stop_min_delta = float(early_stop_min_delta or 0.0)
+        self._stop_best, self._stop_wait, self.should_stop = self._worst, 0, False
         # `devices: N` = N ranks, one per GPU (model.yml:11).  The ranks are started by the CLI (`python -m osu_dreamer_amd
         # fit-denoiser` -> launch.spawn_ranks_if_needed) or by the caller's own torchrun, before anything touches the GPU; inside a rank
         # WORLD_SIZE and `devices` must agree in BOTH directions (devices: 1 under a 4-rank torchrun is a mistake, not a 4-GPU run).
@@ -85,6 +99,8 @@ class Trainer:
             raise RuntimeError(f"trainer.devices={self.devices} but WORLD_SIZE={self.world}: start the run with "
                                "`python -m osu_dreamer_amd fit-denoiser` (it spawns one rank per device) or under "
                                f"`torchrun --nproc-per-node {self.devices}`, and keep trainer.devices equal to the rank count")
+        if early_stop_patience is not None and self.world > 1:
+            raise RuntimeError("early stopping is decided on rank 0's validation: it is implemented for one device")
         self.rank = int(os.environ.get("RANK", "0"))
         self.local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         self.history = []
@@ -199,7 +215,7 @@ class Trainer:
             opt.load_state_dict(ck["optimizer_states"][0])
             sched.load_state_dict(ck["lr_schedulers"][0])
             self.global_step, self.epoch = ck["global_step"], ck["epoch"]
-            self.best_val = ck.get("best_val", float("inf"))
+            self.best_val = ck.get("best_val", self._worst)
         from .ddp import StepAgreement
         if self.world > 1:
             if not hasattr(module, "diffusion"):
@@ -243,13 +259,13 @@ class Trainer:
                         f.write(json.dumps(rec) + "\n")
                 if self.val_check_interval and self.global_step % self.val_check_interval == 0:
                     self._validate_and_checkpoint(module, datamodule, device, opt, sched)
-                if 0 < self.max_steps <= self.global_step:
+                if self.should_stop or 0 < self.max_steps <= self.global_step:
                     done = True
                     break
             self.epoch += 1
             if not self.val_check_interval:
                 self._validate_and_checkpoint(module, datamodule, device, opt, sched)
-            if 0 < self.max_epochs <= self.epoch:
+            if self.should_stop or 0 < self.max_epochs <= self.epoch:
                 done = True
         return self.history
 
@@ -261,9 +277,19 @@ class Trainer:
         self.history.append({"step": self.global_step, **val})
         with open(os.path.join(self.root, "metrics.jsonl"), "a") as f:
             f.write(json.dumps({"step": self.global_step, **val}) + "\n")
-        if self.enable_checkpointing and val.get(self.monitor, float("inf")) < self.best_val:
+        score = val.get(self.monitor, self._worst)
+        if self.enable_checkpointing and self._better(score, self.best_val):
             self.best_val = val[self.monitor]
             self.save_checkpoint(os.path.join(self.root, "checkpoints", "best.ckpt"), module, opt, sched)
+        if self.early_stop_patience is not None:
+            if self._better(score, self._stop_best, self.early_stop_min_delta):
+                self._stop_best, self._stop_wait = score, 0
+            else:
+                self._stop_wait += 1
+                self.should_stop = self._stop_wait >= self.early_stop_patience
+
+    def _better(self, score: float, best: float, min_delta: float = 0.0) -> bool:
+        return score + min_delta < best if self.monitor_mode == "min" else score - min_delta > best
 
 
 def build_from_config(cfg: Dict[str, Any]):
@@ -330,6 +356,41 @@ def fit_style(config: str = DEFAULT_STYLE_CONFIG, ckpt_path: Optional[str] = Non
     return module, trainer
 
 
+def build_latent_from_config(cfg: Dict[str, Any]):
+    from .latent_train import LatentTrainer
+    m = dict(cfg["model"])
+    m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))
+    t = dict(cfg.get("trainer", {}))
+    for k in ("callbacks", "logger", "accumulate_grad_batches", "enable_progress_bar", "enable_model_summary", "benchmark"):
+        t.pop(k, None)
+    t.setdefault("monitor", "eval/score")
+    t.setdefault("monitor_mode", "max")
+    t.setdefault("default_root_dir", "runs/latent")
+    if launch.parse_devices(t.get("devices", 1)) > 1:
+        raise RuntimeError(f"fit-latent trains on one device (trainer.devices={t['devices']}): the reference trains the latent model on one "
+                           "GPU, and the gradient exchange (GradBucketReducer) is tied to the denoiser's arena")
+    module, trainer = LatentTrainer(**m), Trainer(**t)
+    if trainer.precision.startswith("bf16"):
+        module.latent.compute_dtype = torch.bfloat16        # LatentModel does not follow autocast: its compute type is set here
+    return module, trainer
+
+
+def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
+    """begin a training run for the latent model (reference: scripts/fit_latent.py, models/latent/model.yml)."""
+    from .data import BeatmapDataModule
+    with open(config) as f:
+        cfg = yaml.safe_load(f)
+    for k, v in overrides.items():
+        sec, key = k.split("__")
+        cfg.setdefault(sec, {})[key] = v
+    if cfg.get("seed_everything") not in (None, False):
+        seed_everything(cfg["seed_everything"])
+    module, trainer = build_latent_from_config(cfg)
+    data = BeatmapDataModule(**cfg["data"])
+    trainer.fit(module, data, ckpt_path=ckpt_path)
+    return module, trainer
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="osu_dreamer_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -339,6 +400,9 @@ def main(argv=None):
     fs = sub.add_parser("fit-style", help="begin a training run for the style model")
     fs.add_argument("-c", "--config", default=DEFAULT_STYLE_CONFIG)
     fs.add_argument("--ckpt-path", default=None)
+    fl = sub.add_parser("fit-latent", help="begin a training run for the latent model")
+    fl.add_argument("-c", "--config", default=DEFAULT_LATENT_CONFIG)
+    fl.add_argument("--ckpt-path", default=None)
     from . import encode_latents as encode_cmd
     from . import predict as predict_cmd
     encode_cmd.add_parser(sub)
@@ -350,6 +414,9 @@ def main(argv=None):
         return encode_cmd.run(a)
     if a.cmd == "fit-style":
         fit_style(a.config, a.ckpt_path)
+        return
+    if a.cmd == "fit-latent":
+        fit_latent(a.config, a.ckpt_path)
         return
     if a.cmd == "fit-denoiser":
         with open(a.config) as fh:

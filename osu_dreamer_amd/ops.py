@@ -764,3 +764,77 @@ def attn_pool_varlen(scores, values, out, lens, B, L, heads, hd):
     _lens(lens, B)
     _lib.lib().od_attn_pool_varlen(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), _p(lens), B, L,
                                    heads, hd, _stream(scores))
+
+
+# ---------------------------------------------------------------- latent model, training-step kernels (fp32; deterministic sums)
+def _u8(*ts):
+    for t in ts:
+        assert t.dtype == torch.uint8 and t.is_contiguous(), "expected contiguous uint8"
+
+
+def mmd_imq(z, prior, out, dz, ws):
+    """out[0] = MMD^2(z, prior) with the seven IMQ kernels, out[1:4] = its zz / pp / zp terms; dz = its gradient with respect to z."""
+    N, D = z.shape
+    _f32(z, prior, out, dz, ws)
+    assert prior.shape == z.shape == dz.shape and out.numel() >= 4
+    _lib.lib().od_mmd_imq(_p(z), _p(prior), _p(out), _p(dz), _p(ws), ws.numel(), N, D, _stream(z))
+
+
+def scale_by(x, g, y):
+    """y = x * g[0] (g: a device scalar)."""
+    _f32(x, g, y)
+    assert x.shape == y.shape
+    _lib.lib().od_scale_by(_p(x), _p(g), _p(y), x.numel(), _stream(x))
+
+
+def latent_perturb(z, s, eps_z, eps_s, u_s, repl, u_span, u_start, z_out, s_out, masked, start_span, s_noise, z_noise, s_mask_frac,
+                   z_mask_frac, training):
+    """z (B2, E, l) fp32 with any strides; everything else contiguous.  The draws may be None in eval mode (only the swap happens)."""
+    B2, E, l = z.shape
+    S = s.shape[1]
+    assert z.dtype == torch.float32
+    _f32(s, eps_z, eps_s, u_s, repl, u_span, u_start, z_out, s_out)
+    _u8(masked)
+    _i32(start_span)
+    assert tuple(z_out.shape) == (B2, E, l) and tuple(s_out.shape) == (B2, S) and masked.numel() == B2 and start_span.numel() == 2 * B2
+    _lib.lib().od_latent_perturb(_p(z), z.stride(0), z.stride(1), z.stride(2), _p(s), _p(eps_z), _p(eps_s), _p(u_s), _p(repl), _p(u_span),
+                                 _p(u_start), _p(z_out), _p(s_out), _p(masked), _p(start_span), B2, E, l, S, s_noise, z_noise,
+                                 s_mask_frac, z_mask_frac, int(training), _stream(s))
+
+
+def latent_perturb_bwd(dz_out, ds_out, masked, start_span, dz, ds):
+    B2, E, l = dz_out.shape
+    _f32(dz_out, ds_out, dz, ds)
+    _u8(masked)
+    _i32(start_span)
+    _lib.lib().od_latent_perturb_bwd(_p(dz_out), _p(ds_out), _p(masked), _p(start_span), _p(dz), _p(ds), B2, E, l, ds_out.shape[1],
+                                     _stream(ds))
+
+
+def latent_loss_block_frames() -> int:
+    return _lib.lib().cdll.od_latent_loss_block_frames()
+
+
+def latent_loss_ws_floats(B2, L) -> int:
+    return _lib.lib().cdll.od_latent_loss_ws_floats(B2, L)
+
+
+def latent_loss(logits, chart, pred_labels, true_labels, masked, s_reg, loss_ema, ema_init, out, coef, ws, s_reg_weight, training):
+    """out[0:11] the components, out[11] s_reg, out[12] the loss; coef[0:11] the gradient coefficients; loss_ema / ema_init (a uint8 view of
+    the bool flag) are updated on the device when training."""
+    B2, C, L = logits.shape
+    _f32(logits, chart, pred_labels, true_labels, s_reg, loss_ema, out, coef, ws)
+    _u8(masked, ema_init)
+    assert C == 9 and chart.shape == logits.shape and tuple(pred_labels.shape) == tuple(true_labels.shape) == (B2, 5)
+    assert masked.numel() == B2 and loss_ema.numel() == 11 and out.numel() >= 13 and coef.numel() >= 11
+    _lib.lib().od_latent_loss(_p(logits), _p(chart), _p(pred_labels), _p(true_labels), _p(masked), _p(s_reg), _p(loss_ema), _p(ema_init),
+                              _p(out), _p(coef), _p(ws), ws.numel(), B2, L, s_reg_weight, int(training), _stream(logits))
+
+
+def latent_loss_bwd(logits, chart, pred_labels, true_labels, masked, coef, g, dlogits, dlabels, ds_reg, s_reg_weight):
+    B2, _, L = logits.shape
+    _f32(logits, chart, pred_labels, true_labels, coef, g, dlogits, dlabels, ds_reg)
+    _u8(masked)
+    assert dlogits.shape == logits.shape and tuple(dlabels.shape) == (B2, 5)
+    _lib.lib().od_latent_loss_bwd(_p(logits), _p(chart), _p(pred_labels), _p(true_labels), _p(masked), _p(coef), _p(g), _p(dlogits),
+                                  _p(dlabels), _p(ds_reg), B2, L, s_reg_weight, _stream(logits))

@@ -98,3 +98,25 @@ class FusedAdamWEMA(torch.optim.Optimizer):
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+
+
+class ClippedAdamW(torch.optim.AdamW):
+    """`torch.optim.AdamW` with Lightning's `gradient_clip_val` (global norm, clip_grad_norm_) inside step(), and the two hooks
+    `fit.Trainer` drives on every optimizer.  LatentTrainer's optimizer (latent/train.py:156-163): the latent model has no parameter arena,
+    its backward (latent_grad.py) hands each step's gradients to autograd as views of that step's own buffer, so zero_grad always drops
+    `.grad` (the next backward installs the new step's views) and never zeroes a buffer in place."""
+
+    def __init__(self, params, max_grad_norm: Optional[float] = None, **kw):
+        super().__init__(params, **kw)
+        self.max_grad_norm = max_grad_norm
+
+    def zero_grad(self, set_to_none: bool = True):
+        super().zero_grad(set_to_none=True)
+
+    def step(self, closure=None):
+        if self.max_grad_norm:
+            torch.nn.utils.clip_grad_norm_([p for g in self.param_groups for p in g["params"]], float(self.max_grad_norm))
+        return super().step(closure)
+
+    def check_device_status(self):
+        """Nothing to check: no kernel of the latent model's step reports through a device status word."""
