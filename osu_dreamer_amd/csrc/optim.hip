@@ -121,8 +121,10 @@ extern "C" int od_adamw_ema(float* p, const float* g, float* m, float* v, float*
                             float max_norm, const int* status, void* stream) {
     if (step < 1 || n <= 0) return OD_ERR_ARG;
     if (ema_mode != 0 && !ema) return OD_ERR_ARG;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+    // in double, as torch.optim.AdamW forms them: 1.f - powf(beta2, step) cancels (at step 2, 2e-3 is left of 1: half an fp32 ulp of the
+    // power is 1.5e-5 of bc2, 7e-6 of the whole update)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096;
     OD_LAUNCH(adamw_ema_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, eps,
               weight_decay, bc1, bc2_sqrt, ema_decay, ema_mode, gnorm_sq, max_norm, status);

@@ -2,13 +2,14 @@
   * the SIMT-emulator build of the kernel sources (CPU, `-m "not gpu"`), and
   * the real gfx950 library on an MI355X (`-m gpu`).
 """
+import math
 import os
 import subprocess
 
 import pytest
 import torch
 
-from osu_dreamer_amd import _lib
+from osu_dreamer_amd import _lib, det
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(REPO, "tests", "emu")
@@ -114,3 +115,68 @@ def tile_rel_l2(a, b, tr, tc, floor=1e-3, scale=None, floor_max=1e-5):
 
 
 TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2}
+
+
+NAN = float("nan")
+
+
+# ---------------------------------------------------------------- fenced buffers
+class Fenced:
+    """A (rows, cols) view at column 8 of a NaN buffer with >= 24 NaN columns behind it (ld a multiple of 8) and 3 NaN rows below."""
+
+    def __init__(self, rows, cols, dtype, device, fill=None):
+        self.rows, self.cols = rows, cols
+        self.buf = torch.full((rows + 3, (cols + 32 + 7) // 8 * 8), NAN, dtype=dtype, device=device)
+        self.v = self.buf[:rows, 8:8 + cols]
+        if fill is not None:
+            self.v.copy_(fill)
+
+    def check(self, case, what):
+        nan = torch.isnan(self.buf.float())
+        inside = torch.zeros_like(nan)
+        inside[:self.rows, 8:8 + self.cols] = True
+        out = int((~nan & ~inside).sum())
+        assert out == 0, f"{case}: {out} elements outside {what}[{self.rows}, {self.cols}] were written"
+        bad = nan[:self.rows, 8:8 + self.cols]
+        if bool(bad.any()):
+            r, c = (int(i) for i in bad.nonzero()[0])
+            raise AssertionError(f"{case}: {int(bad.sum())} elements of {what} are NaN (unwritten, or read from the poisoned padding), "
+                                 f"first (frame {r}, column {c})")
+
+
+class Flat:
+    """A contiguous tensor of `shape` with 64 NaN elements either side (fp32 vectors: inv_rms, ssg, the weight gradients)."""
+
+    def __init__(self, shape, device, fill=None, dtype=torch.float32):
+        n = math.prod(shape)
+        self.n = n
+        self.buf = torch.full((n + 128,), NAN, dtype=dtype, device=device)
+        self.v = self.buf[64:64 + n].view(*shape)
+        if fill is not None:
+            self.v.copy_(fill)
+
+    def check(self, case, what):
+        assert bool(torch.isnan(self.buf[:64]).all() & torch.isnan(self.buf[64 + self.n:]).all()), f"{case}: written outside {what}"
+        bad = torch.isnan(self.v)
+        assert not bool(bad.any()), f"{case}: {int(bad.sum())} elements of {what} are NaN, first {tuple(int(i) for i in bad.nonzero()[0])}"
+
+
+def bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def det_run(device, on, outs, fn):
+    """fn() with the deterministic shadow on (outs registered, flushed afterwards) or off."""
+    if not on:
+        fn()
+        return
+    try:
+        det.force(True)
+        ctx = det.context(device)
+        for t in outs:
+            ctx.register(t)
+        fn()
+        for t in outs:
+            ctx.flush(t)
+    finally:
+        det.force(None)

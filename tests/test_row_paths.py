@@ -60,7 +60,7 @@ import pytest
 import torch
 
 from osu_dreamer_amd import _lib, det, ops
-from kernel_backend import REPO, block_errors, dev  # noqa: F401
+from kernel_backend import REPO, Fenced, Flat, bits, block_errors, det_run, dev  # noqa: F401
 
 CSRC = os.path.join(REPO, "osu_dreamer_amd", "csrc")
 NAN = float("nan")
@@ -176,51 +176,6 @@ def fix_floor(n):
     return n * 2.0 ** -41
 
 
-# ---------------------------------------------------------------- fenced buffers
-class Fenced:
-    """A (rows, cols) view at column 8 of a NaN buffer with >= 24 NaN columns behind it (ld a multiple of 8) and 3 NaN rows below."""
-
-    def __init__(self, rows, cols, dtype, device, fill=None):
-        self.rows, self.cols = rows, cols
-        self.buf = torch.full((rows + 3, cdiv(cols + 32, 8) * 8), NAN, dtype=dtype, device=device)
-        self.v = self.buf[:rows, 8:8 + cols]
-        if fill is not None:
-            self.v.copy_(fill)
-
-    def check(self, case, what):
-        nan = torch.isnan(self.buf.float())
-        inside = torch.zeros_like(nan)
-        inside[:self.rows, 8:8 + self.cols] = True
-        out = int((~nan & ~inside).sum())
-        assert out == 0, f"{case}: {out} elements outside {what}[{self.rows}, {self.cols}] were written"
-        bad = nan[:self.rows, 8:8 + self.cols]
-        if bool(bad.any()):
-            r, c = (int(i) for i in bad.nonzero()[0])
-            raise AssertionError(f"{case}: {int(bad.sum())} elements of {what} are NaN (unwritten, or read from the poisoned padding), "
-                                 f"first (frame {r}, column {c})")
-
-
-class Flat:
-    """A contiguous tensor of `shape` with 64 NaN elements either side (fp32 vectors: inv_rms, ssg, the weight gradients)."""
-
-    def __init__(self, shape, device, fill=None, dtype=torch.float32):
-        n = math.prod(shape)
-        self.n = n
-        self.buf = torch.full((n + 128,), NAN, dtype=dtype, device=device)
-        self.v = self.buf[64:64 + n].view(*shape)
-        if fill is not None:
-            self.v.copy_(fill)
-
-    def check(self, case, what):
-        assert bool(torch.isnan(self.buf[:64]).all() & torch.isnan(self.buf[64 + self.n:]).all()), f"{case}: written outside {what}"
-        bad = torch.isnan(self.v)
-        assert not bool(bad.any()), f"{case}: {int(bad.sum())} elements of {what} are NaN, first {tuple(int(i) for i in bad.nonzero()[0])}"
-
-
-def bits(t):
-    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
 # ---------------------------------------------------------------- checks
 def check_frames(case, what, out, ref, bound, scale=None):
     """Relative L2 per frame (row of the frame-major layout), with no floor: every frame counts as much as any other."""
@@ -245,23 +200,6 @@ def check_elems(case, what, out, ref, absterms, bound, floor=0.0):
 def check_inv(case, inv, ref):
     rel = ((inv.double() - ref).abs() / ref)
     assert bool((rel <= INV_B).all()), f"{case} inv_rms: worst {float(torch.nan_to_num(rel, nan=float('inf')).max()):.3e} > {INV_B:.3e}"
-
-
-def det_run(device, on, outs, fn):
-    """fn() with the deterministic shadow on (outs registered, flushed afterwards) or off."""
-    if not on:
-        fn()
-        return
-    try:
-        det.force(True)
-        ctx = det.context(device)
-        for t in outs:
-            ctx.register(t)
-        fn()
-        for t in outs:
-            ctx.flush(t)
-    finally:
-        det.force(None)
 
 
 # ---------------------------------------------------------------- operands
