@@ -156,6 +156,7 @@ int od_qk_norm_rope_bwd(int dtype, const void* qkv, int ldqkv, const float* wq, 
 /* q_prescaled != 0: q holds q * scale * log2(e) (od_qk_norm_rope's q_scale), the softmax is the same function of the
  * unscaled q, and od_flash_attn_bwd returns dq as the gradient of that pre-multiplied tensor.
  * o[m][h*hd+d] = softmax(q k^T * scale) v, non-causal, per (b,h); lse fp32 [B][H][L].
+ * Head dims: hd = 32, 64 or 128 for OD_BF16, OD_F32 and OD_F32X3; OD_F16 (half operands) hd = 64 only.  Anything else: OD_ERR_UNSUPPORTED.
  * replaces: attn.py:82 (F.scaled_dot_product_attention). */
 int od_flash_attn_fwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                       float* lse, int B, int H, int L, int hd, float scale, int q_prescaled, void* stream);
@@ -164,7 +165,7 @@ int od_flash_attn_fwd(int dtype, const void* q, int ldq, const void* k, int ldk,
  * same kernel choice (by the padded L) as od_flash_attn_fwd.  replaces: attn.py:82 on sequences zero-padded to a common length. */
 int od_flash_attn_fwd_varlen(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                              float* lse, const int* lens, int B, int H, int L, int hd, float scale, int q_prescaled, void* stream);
-/* dq,dk,dv from do; delta fp32 [B][H][L] is workspace. */
+/* dq,dk,dv from do; delta fp32 [B][H][L] is workspace.  OD_BF16 and OD_F32, hd = 32, 64 or 128 (OD_ERR_UNSUPPORTED otherwise). */
 int od_flash_attn_bwd(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
                       int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk,
                       int lddk, void* dv, int lddv, int B, int H, int L, int hd, float scale, int q_prescaled, void* stream);
@@ -178,7 +179,7 @@ int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const void* k, int 
                           int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk,
                           int lddk, void* dv, int lddv, int B, int H, int L, int hd, float scale, int q_prescaled, void* aux, void* stream);
 /* The same gradients from ONE kernel that executes the 5 algorithmic MFMA passes (od_flash_attn_bwd executes 7: its dQ kernel recomputes S and dP).
- * bf16, head_dim 64 only (OD_ERR_UNSUPPORTED otherwise: call od_flash_attn_bwd).  Each workgroup owns 192 keys; its share of every 64-query
+ * bf16 (or half operands), head_dim 64 only (OD_ERR_UNSUPPORTED otherwise, head_dim 32 and 128 included: call od_flash_attn_bwd).  Each workgroup owns 192 keys; its share of every 64-query
  * dQ tile is added to a running fp32 tile that travels key block -> key block through the XCD's L2 in a fixed order (deterministic, no
  * atomics on data), and the last key block writes dq.  `ws` is caller-owned device memory of od_flash_attn_bwd_fused_ws_bytes(...) bytes whose first
  * *zero_out bytes are zero before the first call; one workspace serves any number of calls of ONE (B, H, L) on one stream (zero it again

@@ -2,7 +2,7 @@
 // F.scaled_dot_product_attention) — forward, and backward as two kernels (dK/dV owned by
 // key tiles, dQ owned by query tiles; no atomics, deterministic).
 //
-// Layout: q/k/v/o are frame-major rows with heads as 64-feature column groups:
+// Layout: q/k/v/o are frame-major rows with heads as HD-feature column groups (HD = 32, 64 or 128):
 //   element (b, h, l, d) at base[(b*L + l)*ld + h*HD + d].
 //
 // MFMA formulation (16x16 tiles, 32-deep K slabs, od_frag<T>): every product is arranged
@@ -89,6 +89,10 @@ __device__ __forceinline__ bool attn_block_coords(int ntiles, int BH, int& tile,
     return bh < BH;
 }
 inline int attn_grid(int ntiles, int BH) { return ((BH + 7) / 8) * 8 * ntiles; }
+// Waves per SIMD asked of the register allocator.  A workgroup whose LDS takes more than half of the CU's 160 KiB (fp32 tensors at head_dim 128:
+// 128 KiB forward, 128.5 KiB dK/dV, 96 KiB dQ) runs alone on its CU whatever its registers, so it asks for one wave per SIMD and may use the whole
+// 512-entry register file; every other instantiation keeps `want`.
+constexpr int attn_occ(int lds_bytes, int want) { return 2 * lds_bytes > 160 * 1024 ? 1 : want; }
 
 // store 4 consecutive features
 __device__ __forceinline__ void st4(bf16_t* p, float a, float b, float c, float d) {
@@ -124,7 +128,7 @@ __device__ __forceinline__ void attn_zero_rows(void* o, int ldo, float* lse, int
 // PRE: q arrives multiplied by scale*log2(e) (od_qk_norm_rope's q_scale), so q.k is already the base-2 exponent and
 // the per-element multiply disappears from the loop.
 template <class T, int HD, int NW, bool PRE, int NQT = 2, bool VL = false>
-__global__ __launch_bounds__(64 * NW, (NW >= 6 || NQT == 1 ? 3 : 2)) void flash_fwd_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
+__global__ __launch_bounds__(64 * NW, attn_occ(4 * Stage<T, HD>::BYTES, (NW >= 6 || NQT == 1 ? 3 : 2))) void flash_fwd_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                            const T* __restrict__ v, int ldv, T* __restrict__ o, int ldo,
                                                            float* __restrict__ lse, int B, int H, int L, float scale,
                                                            const int* __restrict__ lens = nullptr) {
@@ -736,16 +740,20 @@ __global__ __launch_bounds__(64 * NW, (NQB == 1 ? 2 : OD_FWD32_OCC2)) void flash
 // Round 6 ("build the thing, or retire the question with a measurement"): 7.64 against 8.01 ms per call at B = 32 x L = 8192 on
 // one box, 311.6 against 314.6 ms per step (profiles/r06g_ab_fwd16x.txt) — the 16x16x32 MFMA draws ~7 % less per FLOP on a board whose power cap
 // sets the clock (profiles/r03u_mfma_power.txt), which the issue model of round 2 (twice the MFMA issue slots: -12 %) did not know about.
-// bf16 or IEEE-half operands (TA), head_dim 64, q pre-multiplied by scale * log2(e).
-template <int NW, int NQT, class TA, bool VL = false>
+// bf16 or IEEE-half operands (TA), head_dim 64, q pre-multiplied by scale * log2(e).  HD = 128 (bf16): the same kernel on 64 x 128 tiles (16 KiB per
+// operand, four one-KiB pieces per wave), 4 slabs per score and 8 output tiles per query tile.
+template <int NW, int NQT, class TA, bool VL = false, int HD = 64>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ k, int ldk,
                                                                   const bf16_t* __restrict__ v, int ldv, bf16_t* __restrict__ o, int ldo,
                                                                   float* __restrict__ lse, int B, int H, int L,
                                                                   const int* __restrict__ lens = nullptr) {
     using T = TA;                                   // the MFMA operand type: q, k, v hold bf16 or IEEE half (same 16-bit containers); o is bf16
-    using St = Stage<bf16_t, 64>;
-    constexpr int HD = 64, QB = NW * 16 * NQT, STAGE = 2 * St::BYTES;
-    static_assert(NW == 4 || NW == 8, "the K / V tiles are streamed as 2 + 2 (four waves) or 1 + 1 (eight waves) one-KiB pieces per wave");
+    using St = Stage<bf16_t, HD>;
+    constexpr int QB = NW * 16 * NQT, STAGE = 2 * St::BYTES, NS = HD / 32, ND = HD / 16;
+    // one-KiB pieces of a 64-row tile: RPP rows each, PPW per wave and operand (head_dim 64: 2 + 2 with four waves, 1 + 1 with eight; 128: 4 + 4)
+    constexpr int RPP = 1024 / St::ROWB, PPW = St::BYTES / 1024 / NW;
+    static_assert((NW == 4 || NW == 8) && PPW * NW * 1024 == St::BYTES, "the K / V tiles are streamed as whole one-KiB pieces per wave");
+    static_assert(PPW == 1 || (NW * RPP) % St::CPR == 0, "a wave's pieces must share the swizzle's row bits");
     OD_DYN_SMEM(smem);
     const int nqt = (L + QB - 1) / QB;
     int qt, bh;
@@ -758,30 +766,31 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
     const int q0 = qt * QB + wave * 16 * NQT;
     const od_srd_t rk = od_make_srd(k + (size_t)b * L * ldk + h * HD, (unsigned)(((size_t)(Lb - 1) * ldk + HD) * 2));
     const od_srd_t rv = od_make_srd(v + (size_t)b * L * ldv + h * HD, (unsigned)(((size_t)(Lb - 1) * ldv + HD) * 2));
-    // piece = 8 rows x 128 B, tile_off<128>'s swizzle (slot ^ (row & 7), row & 7 = lane >> 3) applied on the SOURCE column; a wave moves pieces w, w + 4
-    const int prow = lane >> 3, pslot = (lane & 7) ^ prow;
-    const unsigned vk = (unsigned)((wave * 8 + prow) * ldk * 2 + pslot * 16), vv = (unsigned)((wave * 8 + prow) * ldv * 2 + pslot * 16);
+    // piece = RPP rows x ROWB bytes (8 x 128 B; head_dim 128: 4 x 256 B), tile_off<ROWB>'s swizzle (slot ^ (row & (CPR - 1))) applied on the SOURCE
+    // column; a wave moves pieces w, w + NW, ...: their rows differ by multiples of CPR, so one per-lane offset serves them all
+    const int prow = lane / St::CPR, pslot = (lane % St::CPR) ^ ((wave * RPP + prow) & (St::CPR - 1));
+    const unsigned vk = (unsigned)((wave * RPP + prow) * ldk * 2 + pslot * 16), vv = (unsigned)((wave * RPP + prow) * ldv * 2 + pslot * 16);
     auto dma = [&](int kt, unsigned char* st) {
         const unsigned sk = (unsigned)kt * 64u * (unsigned)ldk * 2u, sv = (unsigned)kt * 64u * (unsigned)ldv * 2u;
-        od_buffer_lds16(rk, vk, sk, st + wave * 1024);
-        if (NW == 4) od_buffer_lds16(rk, vk, sk + 32u * (unsigned)ldk * 2u, st + (wave + 4) * 1024);
-        od_buffer_lds16(rv, vv, sv, st + St::BYTES + wave * 1024);
-        if (NW == 4) od_buffer_lds16(rv, vv, sv + 32u * (unsigned)ldv * 2u, st + St::BYTES + (wave + 4) * 1024);
+#pragma unroll
+        for (int i = 0; i < PPW; i++) od_buffer_lds16(rk, vk, sk + (unsigned)(i * NW * RPP) * (unsigned)ldk * 2u, st + (wave + NW * i) * 1024);
+#pragma unroll
+        for (int i = 0; i < PPW; i++) od_buffer_lds16(rv, vv, sv + (unsigned)(i * NW * RPP) * (unsigned)ldv * 2u, st + St::BYTES + (wave + NW * i) * 1024);
     };
-    od_frag<T> fq[NQT][2];
+    od_frag<T> fq[NQT][NS];
 #pragma unroll
     for (int qi = 0; qi < NQT; qi++) {
         int row = q0 + qi * 16 + x; row = row < Lb ? row : Lb - 1;
 #pragma unroll
-        for (int s2 = 0; s2 < 2; s2++) od_frag_load(fq[qi][s2], (const TA*)(qb + (size_t)row * ldq + s2 * 32 + g * 8));
+        for (int s2 = 0; s2 < NS; s2++) od_frag_load(fq[qi][s2], (const TA*)(qb + (size_t)row * ldq + s2 * 32 + g * 8));
     }
-    f32x4 oacc[NQT][4];
+    f32x4 oacc[NQT][ND];
     float mref[NQT], lrun[NQT];                     // mref in log2 units (q is pre-multiplied)
 #pragma unroll
     for (int qi = 0; qi < NQT; qi++) {
         mref[qi] = 0.f; lrun[qi] = 0.f;
 #pragma unroll
-        for (int dt = 0; dt < 4; dt++) oacc[qi][dt] = (f32x4)(0.f);
+        for (int dt = 0; dt < ND; dt++) oacc[qi][dt] = (f32x4)(0.f);
     }
     const int nkt = (Lb + 63) / 64;
     OD_DRAIN_VMEM();                                // the Q fragments: a wait hipcc sees (see flash_fwd32_kernel)
@@ -798,14 +807,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
         f32x4 e[NQT][4];
 #pragma unroll
         for (int t4 = 0; t4 < 4; t4++) {
-            od_frag<T> fk[2];
+            od_frag<T> fk[NS];
 #pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) frag_contig<128>(fk[s2], tK, t4 * 16 + x, s2 * 32 + g * 8);
+            for (int s2 = 0; s2 < NS; s2++) frag_contig<St::ROWB>(fk[s2], tK, t4 * 16 + x, s2 * 32 + g * 8);
 #pragma unroll
             for (int qi = 0; qi < NQT; qi++) {
                 f32x4 a = (f32x4)(-mref[qi]);
 #pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) a = od_mma(fk[s2], fq[qi][s2], a);
+                for (int s2 = 0; s2 < NS; s2++) a = od_mma(fk[s2], fq[qi][s2], a);
                 e[qi][t4] = a;
             }
         }
@@ -834,7 +843,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
                     const float alpha = od_exp2(-d);
                     lrun[qi] *= alpha;
 #pragma unroll
-                    for (int dt = 0; dt < 4; dt++) oacc[qi][dt] *= alpha;
+                    for (int dt = 0; dt < ND; dt++) oacc[qi][dt] *= alpha;
                 }
                 mref[qi] += d;
 #pragma unroll
@@ -860,11 +869,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
         }
         // O^T += V^T P^T
 #pragma unroll
-        for (int dt = 0; dt < 4; dt++)
+        for (int dt = 0; dt < ND; dt++)
 #pragma unroll
             for (int u = 0; u < 2; u++) {
                 od_frag<T> fv;
-                frag_cols<128, 128>(fv, tV, tV, dt * 16, x, u, g);
+                frag_cols<St::ROWB, St::ROWB>(fv, tV, tV, dt * 16, x, u, g);
 #pragma unroll
                 for (int qi = 0; qi < NQT; qi++) oacc[qi][dt] = od_mma(fv, fp[qi][u], oacc[qi][dt]);
             }
@@ -894,7 +903,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
             const bool z = VL && row >= Lb;             // padded query rows: zeros, by selection
             bf16_t* orow = o + ((size_t)b * L + row) * ldo + h * HD;
 #pragma unroll
-            for (int dt = 0; dt < 4; dt++)
+            for (int dt = 0; dt < ND; dt++)
                 st4(orow + dt * 16 + 4 * g, z ? 0.f : oacc[qi][dt][0] * inv, z ? 0.f : oacc[qi][dt][1] * inv, z ? 0.f : oacc[qi][dt][2] * inv,
                     z ? 0.f : oacc[qi][dt][3] * inv);
             if (g == 0) lse[((size_t)b * H + h) * L + row] = z ? 0.f : (mref[qi] + log2f(l)) * LN2;
@@ -930,11 +939,13 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o
 }
 
 #define OD_BWD_LOOP_SYNC() __syncthreads()
+// Registers: the dK / dV accumulators alone take NK * HD / 2.  Past 128 of them (head_dim 128 with more than 16 keys per wave) two waves per SIMD
+// no longer fit without scratch, and the kernel asks for one wave per SIMD and the whole register file instead (accumulators in AGPRs).
 // dK, dV: block owns 4 waves x NK*16 keys; loop over 64-query tiles.
 //   S = Q K^T (cols = keys) ; dV^T += dO^T P ; dP = dO V^T ; dS = P*(dP - delta)*scale ; dK^T += Q^T dS
 // LDS per stage: Q, dO row-major (+ Q^T, dO^T for f32); bf16 double-buffers the stage.
 template <class T, int HD, int NK, int NWK, bool PRE>
-__global__ __launch_bounds__(64 * NWK, (NWK == 8 ? 1 : 2)) void flash_bwd_dkv_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
+__global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2 + 2 * Stage<T, HD>::NT) * Stage<T, HD>::BYTES + 512), (NWK == 8 || NK * HD > 256 ? 1 : 2))) void flash_bwd_dkv_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                                const T* __restrict__ v, int ldv, const T* __restrict__ dout, int lddo,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                T* __restrict__ dk, int lddk, T* __restrict__ dv, int lddv,
@@ -1117,7 +1128,7 @@ __global__ __launch_bounds__(64 * NWK, (NWK == 8 ? 1 : 2)) void flash_bwd_dkv_ke
 // dQ: block owns 4 waves x NQ*16 queries; loop over 64-key tiles.
 //   S^T = K Q^T ; dP^T = V dO^T ; dS^T = P^T*(dP^T - delta)*scale ; dQ^T += K^T dS^T
 template <class T, int HD, int NQ, int NW, bool PRE>
-__global__ __launch_bounds__(64 * NW, (NW >= 6 ? 3 : 2)) void flash_bwd_dq_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
+__global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 + Stage<T, HD>::NT) * Stage<T, HD>::BYTES, (NW >= 6 ? 3 : 2))) void flash_bwd_dq_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                               const T* __restrict__ v, int ldv, const T* __restrict__ dout, int lddo,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               T* __restrict__ dq, int lddq, int B, int H, int L, float scale) {
@@ -1303,6 +1314,18 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
         return 0;
       }
     }
+    // bf16, head_dim 128, pre-multiplied q (what the engine passes): the 16x16x32 form at every length.  At B = 32 x L = 8192, 8 heads of 128 against
+    // 16 heads of 64 in one process (tools/mb_attn_hd128.py, profiles/r11_attn_hd128.txt): 7.29-7.41 ms against 7.53-7.63 (0.97 x); the generic
+    // flash_fwd_kernel<bf16_t, 128> below ran 8.43 ms with 32 queries per wave and 11.7 with 16, and stays for q that is not pre-multiplied.
+    // At the sampler's B = 4 x L = 1115: 38 against 43 us.  208 registers, two waves per SIMD, two 64-KiB workgroups per CU.
+    if constexpr (std::is_same<T, bf16_t>::value && HD == 128 && PRE) {
+        constexpr int NQT = 2;
+        const int grid = attn_grid((L + 4 * 16 * NQT - 1) / (4 * 16 * NQT), B * H);
+        OD_LAUNCH_DYN((flash_fwd16x_kernel<4, NQT, bf16_t, VL, 128>), dim3(grid), dim3(256), (4 * Stage<T, HD>::BYTES), st, (const bf16_t*)q, ldq,
+                      (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, B, H, L, lens);
+        OD_CHECK_LAUNCH();
+        return 0;
+    }
     if constexpr (std::is_same<T, bf16_t>::value && HD == 64) {
         constexpr int NW = OD_FWD32_NW, NQB = OD_FWD32_NQB;
         const int grid = attn_grid((L + NW * NQB * 32 - 1) / (NW * NQB * 32), B * H);
@@ -1390,6 +1413,9 @@ extern "C" int od_flash_attn_fwd(int dtype, const void* q, int ldq, const void* 
     if (dtype == OD_F32 && hd == 32) return FWD(float, 32);
     if (dtype == OD_F32X3 && hd == 64) return FWD(f32x3_t, 64);
     if (dtype == OD_F32X3 && hd == 32) return FWD(f32x3_t, 32);
+    if (dtype == OD_BF16 && hd == 128) return FWD(bf16_t, 128);
+    if (dtype == OD_F32 && hd == 128) return FWD(float, 128);
+    if (dtype == OD_F32X3 && hd == 128) return FWD(f32x3_t, 128);
 #undef FWD
     return OD_ERR_UNSUPPORTED;
 }
@@ -1409,6 +1435,9 @@ extern "C" int od_flash_attn_fwd_varlen(int dtype, const void* q, int ldq, const
     if (dtype == OD_F32 && hd == 32) return FWD(float, 32);
     if (dtype == OD_F32X3 && hd == 64) return FWD(f32x3_t, 64);
     if (dtype == OD_F32X3 && hd == 32) return FWD(f32x3_t, 32);
+    if (dtype == OD_BF16 && hd == 128) return FWD(bf16_t, 128);
+    if (dtype == OD_F32 && hd == 128) return FWD(float, 128);
+    if (dtype == OD_F32X3 && hd == 128) return FWD(f32x3_t, 128);
 #undef FWD
     return OD_ERR_UNSUPPORTED;
 }
@@ -1468,11 +1497,23 @@ extern "C" int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const vo
 #ifndef OD_BWD_NQ
 #define OD_BWD_NQ 4
 #endif
+// bf16 / hd 128: the same lever.  dK/dV: 16 keys per wave at two waves per SIMD (228 VGPRs; 32 keys: 360 B of scratch) ran the pair at 29.4-32.0 ms
+// per call (B = 32, H = 8, L = 8192); at ONE wave per SIMD 32 keys 29.2 and 48 keys (254 VGPRs + 204 AGPRs, no scratch) 26.3-26.7: taken.  dQ: 32 queries
+// at two waves per SIMD (252-256 VGPRs) 29.1 against 32.0 with 16; 48 / 64 queries at one wave per SIMD 28.5 / 26.2 against 26.3: not taken.
+// The head_dim-64 pair on the same boxes: 23.8-24.8 (profiles/r11_attn_hd128.txt).
+#ifndef OD_BWD128_NK
+#define OD_BWD128_NK 3
+#endif
+#ifndef OD_BWD128_NQ
+#define OD_BWD128_NQ 2
+#endif
 #define BWD(TT, HDV, NKV, NQV) (q_prescaled ? launch_bwd<TT, HDV, NKV, NQV, true>(ARGS) : launch_bwd<TT, HDV, NKV, NQV, false>(ARGS))
     if (dtype == OD_BF16 && hd == 64) return BWD(bf16_t, 64, OD_BWD_NK, OD_BWD_NQ);
     if (dtype == OD_BF16 && hd == 32) return BWD(bf16_t, 32, 2, 2);
     if (dtype == OD_F32 && hd == 64) return BWD(float, 64, 1, 1);
     if (dtype == OD_F32 && hd == 32) return BWD(float, 32, 1, 1);
+    if (dtype == OD_BF16 && hd == 128) return BWD(bf16_t, 128, OD_BWD128_NK, OD_BWD128_NQ);
+    if (dtype == OD_F32 && hd == 128) return BWD(float, 128, 1, 1);
 #undef BWD
 #undef ARGS
     return OD_ERR_UNSUPPORTED;

@@ -272,7 +272,9 @@ class DenoiserEngine:
             #     kernel that closed the previous layer
             qkv = self.lbuf("qkv", i, (M, 3 * dh))
             if self.train or self.attn_f16 or self.hd not in (32, 64) or (2 * dh) % 128:
-                # backward needs the pre-norm q, k as well.  attn_f16: qk and the v columns of qkv are written as IEEE half
+                # backward needs the pre-norm q, k as well.  attn_f16: qk and the v columns of qkv are written as IEEE half.
+                # head_dim 128 (any head dim the GEMM's norm + RoPE epilogue has no form for) takes this path without grad too:
+                # od_gemm_nt + od_qk_norm_rope inside the library, then the head_dim-128 attention kernels
                 qk = self.lbuf("qk16" if self.attn_f16 else "qk", i, (M, 2 * dh), torch.float16 if self.attn_f16 else None)
                 ops.gemm_nt_qkrope_split(h1, self.W(p + "attn.qkv_proj"), self.P(p + "attn.qkv_proj.bias"), qkv, qk,
                                          self.P(p + "attn.q_norm.weight"), self.P(p + "attn.k_norm.weight"), tab, L, self.H,
@@ -369,7 +371,7 @@ class DenoiserEngine:
         L = 2048: 1.64-1.70 against 1.71-1.88 ms; 4096: 5.7 against 6.3-6.4; 8192: 21.0-21.4 against 23.3-24.1; batch 8 x 32768: 81.0 against 94.0.
         (Shorter sequences have not been measured: they run the chain in lock step — a key block trails its predecessor by ~1.5 query tiles and
         consecutive key blocks start (L / 64) / (CUs per XCD) tiles apart.)
-        OD_ATTN_BWD_FUSED=0 / 1 forces the two-kernel / the fused path."""
+        OD_ATTN_BWD_FUSED=0 / 1 forces the two-kernel / the fused path.  head_dim 32 and 128 have no fused form: the kernel pair at every L."""
         import os
         if self.dtype != torch.bfloat16 or self.hd != 64:
             return False
