@@ -178,6 +178,15 @@ int od_attn_aux_destroy(void* aux);
 int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
                           int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk,
                           int lddk, void* dv, int lddv, int B, int H, int L, int hd, float scale, int q_prescaled, void* aux, void* stream);
+/* Varlen form of od_flash_attn_bwd_aux (aux = NULL allowed): sequence b of the padded (B, L) layout is valid for rows < lens[b] (device int32
+ * [B], 1 <= lens[b] <= L; L stays the row stride).  Keys at or past lens[b] are never read; query rows there are skipped (their lse is 0), not
+ * multiplied by zero; rows >= lens[b] of dq, dk and dv are written as zeros.  The same kernel pair, tile sizes and (dtype, hd) set as
+ * od_flash_attn_bwd; with every lens[b] == L the result is that call's, bit for bit.
+ * replaces: autograd of attn.py:82 on sequences zero-padded to a common length. */
+int od_flash_attn_bwd_varlen(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                             int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk,
+                             int lddk, void* dv, int lddv, const int* lens, int B, int H, int L, int hd, float scale, int q_prescaled,
+                             void* aux, void* stream);
 /* The same gradients from ONE kernel that executes the 5 algorithmic MFMA passes (od_flash_attn_bwd executes 7: its dQ kernel recomputes S and dP).
  * bf16 (or half operands), head_dim 64 only (OD_ERR_UNSUPPORTED otherwise, head_dim 32 and 128 included: call od_flash_attn_bwd).  Each workgroup owns 192 keys; its share of every 64-query
  * dQ tile is added to a running fp32 tile that travels key block -> key block through the XCD's L2 in a fixed order (deterministic, no
@@ -214,6 +223,10 @@ int od_dwconv_varlen(int dtype, const void* x, int ldx, const float* w, const fl
                      int B, int L, int C, int ksize, void* stream);
 int od_dwconv_bwd(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx,
                   float* dw, float* db, int B, int L, int C, int ksize, void* stream);
+/* the same per sequence of valid length lens[b]: taps of x and dy at frames >= lens[b] read as zero (selected: those rows are never
+ * loaded) and dx there is written as zero.  replaces: autograd of swiglu.py:20 on sequences zero-padded to a common length. */
+int od_dwconv_bwd_varlen(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx,
+                         float* dw, float* db, const int* lens, int B, int L, int C, int ksize, void* stream);
 /* x[(b,l)][c] *= scale[b][c] in place (scale fp32 [B][C]): nn.Dropout1d in training mode — the host draws 0 or 1/(1-p) per
  * (sample, channel); the same call is its backward.  replaces: swiglu.py:23,30. */
 int od_scale_channels(int dtype, void* x, int ldx, const float* scale, int B, int L, int C, void* stream);
@@ -243,6 +256,12 @@ int od_uhead_fwd_varlen(const float* xt, const float* w0, const float* b0, const
 int od_uhead_bwd(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
                  const float* b3, const float* w4, const float* b4, const float* dfm, float* dw0, float* db0, float* dw1,
                  float* db1, float* dw3, float* db3, float* dw4, float* db4, int B, int E, int L, int U, void* stream);
+/* the same with the mean over frames < lens[b] and both k = 3 convs zero-padded at lens[b]; frames >= lens[b] of xt are never read.
+ * replaces: autograd of model.py:58-65,99 per sequence. */
+int od_uhead_bwd_varlen(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
+                        const float* b3, const float* w4, const float* b4, const float* dfm, float* dw0, float* db0, float* dw1,
+                        float* db1, float* dw3, float* db3, float* dw4, float* db4, const int* lens, int B, int E, int L, int U,
+                        void* stream);
 /* u[b] = u_scale*softplus(w_out . (f*(1+mod[0:U]) + mod[U:2U]) + b_out), f = fsum/L.  replaces: model.py:100-102. */
 int od_uhead_tail(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, int B, int U,
                   int L, float u_scale, void* stream);
@@ -253,13 +272,25 @@ int od_uhead_tail_varlen(const float* fsum, const float* mod, const float* w_out
 int od_uhead_tail_bwd(const float* fsum, const float* mod, const float* w_out, const float* b_out, const float* du,
                       float* dfm, float* dmod, float* dw_out, float* db_out, int B, int U, int L, float u_scale,
                       void* stream);
+/* the same with f = fsum/lens[b].  replaces: autograd of model.py:99-102 (the mean over a sequence's own frames). */
+int od_uhead_tail_bwd_varlen(const float* fsum, const float* mod, const float* w_out, const float* b_out, const float* du,
+                             float* dfm, float* dmod, float* dw_out, float* db_out, const int* lens, int B, int U, int L,
+                             float u_scale, void* stream);
 
 /* ---- diffusion loss + sampler (models/diffusion/train.py:69-108, model.py:117-138) -- */
 /* xt = lerp(x0,x1,t[b]); dsq[b] = frame_dist_sq(xt,x1).  (dsq must be zeroed by the caller.) */
 int od_make_xt(const float* x0, const float* x1, const float* t, float* xt, float* dsq, int B, int E, int L, void* stream);
+/* the same per sequence: dsq[b] is the mean over frames < lens[b]; xt at frames >= lens[b] is written as 0 and x0 / x1 there are not
+ * read (they may hold anything).  replaces: train.py:83-87 on one sequence of a zero-padded batch. */
+int od_make_xt_varlen(const float* x0, const float* x1, const float* t, float* xt, float* dsq, const int* lens, int B, int E, int L,
+                      void* stream);
 /* sums[b][0..2] += (S1, S2, dS1/du) ; dv = dLoss/dv_pred.  Needs dsq complete. */
 int od_loss_grad(const float* xt, const float* x1, const float* u, const float* v, const float* dsq, float* dv,
                  float* sums, int B, int E, int L, float c0, float osl_w, float del_w, void* stream);
+/* the same per sequence: the sums run over frames < lens[b] and are normalised by lens[b]; dv at frames >= lens[b] is written as 0 and
+ * x1 / v there are not read.  od_loss_finalize follows unchanged.  replaces: train.py:89-101 on one sequence of a zero-padded batch. */
+int od_loss_grad_varlen(const float* xt, const float* x1, const float* u, const float* v, const float* dsq, float* dv,
+                        float* sums, const int* lens, int B, int E, int L, float c0, float osl_w, float del_w, void* stream);
 /* out[0..3] = loss, osl, del, u_mape; du[b] = dLoss/du_pred. */
 int od_loss_finalize(const float* sums, const float* dsq, const float* u, float* out, float* du, int B, float c0,
                      float osl_w, float del_w, void* stream);

@@ -915,19 +915,22 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 1 : 2)) void flash_fwd16x_kerne
 // 4-deep LDS ring — measured 8.36 ms against 7.9-8.1 and was removed: profiles/r02g_ab_pingpong.txt.)
 
 // delta[b][h][l] = sum_d dO*O  — one wave per frame row, lanes over (h, d) chunks of 8
-template <class T>
+// VL: rows at or past lens[b] are not read; their delta is written as 0
+template <class T, bool VL = false>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o, int ldo, const T* __restrict__ dout, int lddo,
-                                                         float* __restrict__ delta, int B, int H, int L, int HD) {
+                                                         float* __restrict__ delta, int B, int H, int L, int HD, const int* __restrict__ lens = nullptr) {
     const int lane = threadIdx.x & 63;
     const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= (long)B * L) return;
     const int b = (int)(m / L), l = (int)(m % L);
     const int lph = HD / 8, nch = H * lph;
+    bool pad = false;
+    if constexpr (VL) pad = l >= od_uniform(lens[b]);
     for (int it = 0; it * 64 < nch; it++) {
         const int qd = it * 64 + lane;
         const bool act = qd < nch;
         float s = 0.f;
-        if (act) {
+        if (act && !pad) {
             float a[8], d[8];
             od_ld8(o + m * ldo + qd * 8, a); od_ld8(dout + m * lddo + qd * 8, d);
 #pragma unroll
@@ -939,17 +942,27 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T* __restrict__ o
 }
 
 #define OD_BWD_LOOP_SYNC() __syncthreads()
+// varlen backward: rows r0 .. r0 + nrows - 1 (below L) of head h of a gradient, as zeros
+template <class T, int HD>
+__device__ __forceinline__ void attn_zero_grad_rows(T* d, int ldd, int b, int h, int L, int r0, int nrows) {
+    constexpr int CPR = HD * (int)sizeof(T) / 16, EPC = 16 / (int)sizeof(T);
+    const int r1 = r0 + nrows < L ? r0 + nrows : L;
+    for (int i = threadIdx.x; i < (r1 - r0) * CPR; i += blockDim.x) {
+        const int row = r0 + i / CPR, ch = i % CPR;
+        *(u32x4*)(d + ((size_t)b * L + row) * ldd + h * HD + ch * EPC) = (u32x4)(0u);
+    }
+}
 // Registers: the dK / dV accumulators alone take NK * HD / 2.  Past 128 of them (head_dim 128 with more than 16 keys per wave) two waves per SIMD
 // no longer fit without scratch, and the kernel asks for one wave per SIMD and the whole register file instead (accumulators in AGPRs).
 // dK, dV: block owns 4 waves x NK*16 keys; loop over 64-query tiles.
 //   S = Q K^T (cols = keys) ; dV^T += dO^T P ; dP = dO V^T ; dS = P*(dP - delta)*scale ; dK^T += Q^T dS
 // LDS per stage: Q, dO row-major (+ Q^T, dO^T for f32); bf16 double-buffers the stage.
-template <class T, int HD, int NK, int NWK, bool PRE>
+template <class T, int HD, int NK, int NWK, bool PRE, bool VL = false>
 __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2 + 2 * Stage<T, HD>::NT) * Stage<T, HD>::BYTES + 512), (NWK == 8 || NK * HD > 256 ? 1 : 2))) void flash_bwd_dkv_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                                const T* __restrict__ v, int ldv, const T* __restrict__ dout, int lddo,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                T* __restrict__ dk, int lddk, T* __restrict__ dv, int lddv,
-                                                               int B, int H, int L, float scale) {
+                                                               int B, int H, int L, float scale, const int* __restrict__ lens = nullptr) {
     using St = Stage<T, HD>;
     constexpr int NS = HD / 32, ND = HD / 16, KB = NWK * NK * 16;
     static_assert(NWK == 4 || St::TR, "the register-staged (f32) path assumes 256 threads");
@@ -960,6 +973,18 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
     int ktile, bh;
     if (!attn_block_coords(nkt, B * H, ktile, bh)) return;
     const int b = bh / H, h = bh % H;
+    // VL: sequence b is valid for frames < Lv.  Every bound below (query tiles, key rows, the ragged masks) is Lv; the row strides stay L.
+    // (Lv is a reference: the dense instantiation names L itself and compiles to the instructions it always had — tools/dense_isa_diff.py)
+    int Lb = 0;
+    if constexpr (VL) Lb = od_uniform(lens[b]);
+    const int& Lv = VL ? Lb : L;
+    if constexpr (VL) {
+        if (ktile * KB >= Lv) {                           // a key block of padding alone: zero rows, no loop
+            attn_zero_grad_rows<T, HD>(dk, lddk, b, h, L, ktile * KB, KB);
+            attn_zero_grad_rows<T, HD>(dv, lddv, b, h, L, ktile * KB, KB);
+            return;
+        }
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, x = lane & 15, g = lane >> 4;
     const T* qb = q + (size_t)b * L * ldq + h * HD;
     const T* kb = k + (size_t)b * L * ldk + h * HD;
@@ -978,7 +1003,7 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
     od_frag<T> fk[NK][NS], fv[NK][NS];
 #pragma unroll
     for (int ki = 0; ki < NK; ki++) {
-        int row = key0 + ki * 16 + x; row = row < L ? row : L - 1;
+        int row = key0 + ki * 16 + x; row = row < Lv ? row : Lv - 1;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             od_frag_load(fk[ki][s], kb + (size_t)row * ldk + s * 32 + g * 8);
@@ -991,15 +1016,15 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
 #pragma unroll
         for (int dt = 0; dt < ND; dt++) { dkacc[ki][dt] = (f32x4)(0.f); dvacc[ki][dt] = (f32x4)(0.f); }
 
-    const int nqt = (L + 63) / 64;
+    const int nqt = (Lv + 63) / 64;
     St sq, so;
     float r_lse = 0.f, r_del = 0.f;
     auto gload = [&](int qt) {
-        sq.load(qb, ldq, qt * 64, L); so.load(dob, lddo, qt * 64, L);
+        sq.load(qb, ldq, qt * 64, Lv); so.load(dob, lddo, qt * 64, Lv);
         if (threadIdx.x < 64) {
             const int row = qt * 64 + threadIdx.x;
-            r_lse = row < L ? lseb[row] : 0.f;
-            r_del = row < L ? delb[row] : 0.f;
+            r_lse = row < Lv ? lseb[row] : 0.f;
+            r_del = row < Lv ? delb[row] : 0.f;
         }
     };
     // stage layout: [Q][dO]([Q^T][dO^T])[lse(64) delta(64)]
@@ -1013,8 +1038,8 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
     auto gload_small = [&](int qt) {
         if (threadIdx.x < 64) {
             const int row = qt * 64 + threadIdx.x;
-            r_lse = row < L ? lseb[row] : 0.f;
-            r_del = row < L ? delb[row] : 0.f;
+            r_lse = row < Lv ? lseb[row] : 0.f;
+            r_del = row < Lv ? delb[row] : 0.f;
         }
     };
     auto lstore_small = [&](unsigned char* st) {
@@ -1022,14 +1047,14 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
         if (threadIdx.x < 64) { sl[threadIdx.x] = -r_lse * inv_scale; sl[64 + threadIdx.x] = -r_del; }
     };
     auto dma = [&](int qt, unsigned char* st) {
-        St::template dma_rowmajor<NWK>(qb, ldq, qt * 64, L, st);
-        St::template dma_rowmajor<NWK>(dob, lddo, qt * 64, L, st + St::BYTES);
+        St::template dma_rowmajor<NWK>(qb, ldq, qt * 64, Lv, st);
+        St::template dma_rowmajor<NWK>(dob, lddo, qt * 64, Lv, st + St::BYTES);
     };
     if constexpr (St::TR) { dma(0, smem); gload_small(0); lstore_small(smem); }
     else { gload(0); lstore(smem); }
     __syncthreads();
     int cur = 0;
-    const bool kragged = ktile * KB + KB > L;
+    const bool kragged = ktile * KB + KB > Lv;
     auto tile = [&](int qt, auto masked_t) {
         constexpr bool MASKED = decltype(masked_t)::value;
         if (qt + 1 < nqt) {
@@ -1068,10 +1093,10 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
 #pragma unroll
                 for (int r = 0; r < 4; r++) p[r] = od_exp2(e[r]);
                 if constexpr (MASKED) {
-                    const bool kvalid = key0 + ki * 16 + x < L;
+                    const bool kvalid = key0 + ki * 16 + x < Lv;
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (!(kvalid && (qbase + t4 * 16 + 4 * g + r < L))) p[r] = 0.f;
+                        if (!(kvalid && (qbase + t4 * 16 + 4 * g + r < Lv))) p[r] = 0.f;
                 }
                 const f32x4 ds = od_mul4(p, pa);
                 od_frag_set4(fp[ki][t4 >> 1], t4 & 1, p[0], p[1], p[2], p[3]);
@@ -1100,18 +1125,20 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
         OD_BWD_LOOP_SYNC();
         if (NSTAGE == 2) cur ^= 1;
     };
-    const int nfull = kragged ? 0 : L / 64;
+    const int nfull = kragged ? 0 : Lv / 64;
     for (int qt = 0; qt < nfull; qt++) tile(qt, std::false_type{});
     for (int qt = nfull; qt < nqt; qt++) tile(qt, std::true_type{});
 #pragma unroll
     for (int ki = 0; ki < NK; ki++) {
         const int row = key0 + ki * 16 + x;
         if (row < L) {
+            const bool z = VL && row >= Lv;             // padded key rows: zeros, by selection
             T* dkr = dk + ((size_t)b * L + row) * lddk + h * HD;
             T* dvr = dv + ((size_t)b * L + row) * lddv + h * HD;
 #pragma unroll
             for (int dt = 0; dt < ND; dt++) {
                 dkacc[ki][dt] *= out_scale;
+                if constexpr (VL) { if (z) { dkacc[ki][dt] = (f32x4)(0.f); dvacc[ki][dt] = (f32x4)(0.f); } }
                 st4(dkr + dt * 16 + 4 * g, dkacc[ki][dt][0], dkacc[ki][dt][1], dkacc[ki][dt][2], dkacc[ki][dt][3]);
                 st4(dvr + dt * 16 + 4 * g, dvacc[ki][dt][0], dvacc[ki][dt][1], dvacc[ki][dt][2], dvacc[ki][dt][3]);
             }
@@ -1127,11 +1154,12 @@ __global__ __launch_bounds__(64 * NWK, attn_occ((Stage<T, HD>::TR ? 2 : 1) * ((2
 
 // dQ: block owns 4 waves x NQ*16 queries; loop over 64-key tiles.
 //   S^T = K Q^T ; dP^T = V dO^T ; dS^T = P^T*(dP^T - delta)*scale ; dQ^T += K^T dS^T
-template <class T, int HD, int NQ, int NW, bool PRE>
+template <class T, int HD, int NQ, int NW, bool PRE, bool VL = false>
 __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 + Stage<T, HD>::NT) * Stage<T, HD>::BYTES, (NW >= 6 ? 3 : 2))) void flash_bwd_dq_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k, int ldk,
                                                               const T* __restrict__ v, int ldv, const T* __restrict__ dout, int lddo,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
-                                                              T* __restrict__ dq, int lddq, int B, int H, int L, float scale) {
+                                                              T* __restrict__ dq, int lddq, int B, int H, int L, float scale,
+                                                              const int* __restrict__ lens = nullptr) {
     using St = Stage<T, HD>;
     constexpr int NS = HD / 32, ND = HD / 16, QB = NW * NQ * 16;
     constexpr int NSTAGE = St::TR ? 2 : 1;
@@ -1141,6 +1169,12 @@ __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 +
     int qtile, bh;
     if (!attn_block_coords(nqt, B * H, qtile, bh)) return;
     const int b = bh / H, h = bh % H;
+    int Lb = 0;                                           // VL: as in the dK/dV kernel
+    if constexpr (VL) Lb = od_uniform(lens[b]);
+    const int& Lv = VL ? Lb : L;
+    if constexpr (VL) {
+        if (qtile * QB >= Lv) { attn_zero_grad_rows<T, HD>(dq, lddq, b, h, L, qtile * QB, QB); return; }
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, x = lane & 15, g = lane >> 4;
     const T* qb = q + (size_t)b * L * ldq + h * HD;
     const T* kb = k + (size_t)b * L * ldk + h * HD;
@@ -1154,7 +1188,7 @@ __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 +
     float r_lse[NQ], r_del[NQ];
 #pragma unroll
     for (int qi = 0; qi < NQ; qi++) {
-        int row = q0 + qi * 16 + x; row = row < L ? row : L - 1;
+        int row = q0 + qi * 16 + x; row = row < Lv ? row : Lv - 1;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             od_frag_load(fq[qi][s], qb + (size_t)row * ldq + s * 32 + g * 8);
@@ -1169,25 +1203,25 @@ __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 +
 #pragma unroll
         for (int dt = 0; dt < ND; dt++) dqacc[qi][dt] = (f32x4)(0.f);
 
-    const int nkt = (L + 63) / 64;
+    const int nkt = (Lv + 63) / 64;
     St sk, sv;
     auto lstore = [&](unsigned char* st) {
         sk.store_rowmajor(st); sv.store_rowmajor(st + St::BYTES);
         if constexpr (!St::TR) sk.store_transposed(st + 2 * St::BYTES);
     };
     auto dma = [&](int kt, unsigned char* st) {
-        St::template dma_rowmajor<NW>(kb, ldk, kt * 64, L, st);
-        St::template dma_rowmajor<NW>(vb, ldv, kt * 64, L, st + St::BYTES);
+        St::template dma_rowmajor<NW>(kb, ldk, kt * 64, Lv, st);
+        St::template dma_rowmajor<NW>(vb, ldv, kt * 64, Lv, st + St::BYTES);
     };
     if constexpr (St::TR) dma(0, smem);
-    else { sk.load(kb, ldk, 0, L); sv.load(vb, ldv, 0, L); lstore(smem); }
+    else { sk.load(kb, ldk, 0, Lv); sv.load(vb, ldv, 0, Lv); lstore(smem); }
     __syncthreads();
     int cur = 0;
     auto tile = [&](int kt, auto masked_t) {
         constexpr bool MASKED = decltype(masked_t)::value;
         if (kt + 1 < nkt) {
             if constexpr (St::TR) dma(kt + 1, smem + (cur ^ 1) * STAGE);
-            else { sk.load(kb, ldk, (kt + 1) * 64, L); sv.load(vb, ldv, (kt + 1) * 64, L); }
+            else { sk.load(kb, ldk, (kt + 1) * 64, Lv); sv.load(vb, ldv, (kt + 1) * 64, Lv); }
         }
         const unsigned char* st = smem + cur * STAGE;
         const unsigned char* tK = st;
@@ -1216,7 +1250,7 @@ __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 +
                 if constexpr (MASKED) {
 #pragma unroll
                     for (int r = 0; r < 4; r++)
-                        if (kbase + t4 * 16 + 4 * g + r >= L) p[r] = 0.f;
+                        if (kbase + t4 * 16 + 4 * g + r >= Lv) p[r] = 0.f;
                 }
                 const f32x4 ds = od_mul4(p, pa);
                 od_frag_set4(fds[qi][t4 >> 1], t4 & 1, ds[0], ds[1], ds[2], ds[3]);
@@ -1236,17 +1270,19 @@ __global__ __launch_bounds__(64 * NW, attn_occ((Stage<T, HD>::TR ? 2 : 1) * (2 +
         OD_BWD_LOOP_SYNC();
         if (NSTAGE == 2) cur ^= 1;
     };
-    const int nfull = L / 64;
+    const int nfull = Lv / 64;
     for (int kt = 0; kt < nfull; kt++) tile(kt, std::false_type{});
     if (nfull < nkt) tile(nfull, std::true_type{});
 #pragma unroll
     for (int qi = 0; qi < NQ; qi++) {
         const int row = q0 + qi * 16 + x;
         if (row < L) {
+            const bool z = VL && row >= Lv;             // padded query rows: zeros, by selection (their accumulators repeat row Lv - 1)
             T* dqr = dq + ((size_t)b * L + row) * lddq + h * HD;
 #pragma unroll
             for (int dt = 0; dt < ND; dt++) {
                 dqacc[qi][dt] *= out_scale;
+                if constexpr (VL) { if (z) dqacc[qi][dt] = (f32x4)(0.f); }
                 st4(dqr + dt * 16 + 4 * g, dqacc[qi][dt][0], dqacc[qi][dt][1], dqacc[qi][dt][2], dqacc[qi][dt][3]);
             }
         }
@@ -1364,13 +1400,14 @@ int launch_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
     }
 }
 
-template <class T, int HD, int NK, int NQ, bool PRE>
+// VL: the varlen form (lens = device int32 [B]); the same kernel pair and tile sizes as the dense call of the padded L
+template <class T, int HD, int NK, int NQ, bool PRE, bool VL = false>
 int launch_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo, const void* dout,
                int lddo, const float* lse, float* delta, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int H,
-               int L, float scale, hipStream_t st, const AttnAux* aux = nullptr) {
+               int L, float scale, hipStream_t st, const AttnAux* aux = nullptr, const int* lens = nullptr) {
     const long M = (long)B * L;
-    OD_LAUNCH((attn_delta_kernel<T>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const T*)o, ldo, (const T*)dout, lddo, delta,
-              B, H, L, HD);
+    OD_LAUNCH((attn_delta_kernel<T, VL>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const T*)o, ldo, (const T*)dout, lddo, delta,
+              B, H, L, HD, lens);
     // Two-stream form: with a side stream (od_attn_aux_create) the dQ kernel runs beside the dK/dV kernel — both depend on delta alone — and its
     // workgroups fill the CUs the other kernel's last block round leaves idle: 24.69 -> 24.43 ms per layer (profiles/r03h_ab_bwd_two_streams.txt).
     hipStream_t st_q = st;
@@ -1383,14 +1420,14 @@ int launch_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, in
 #endif
     constexpr int NWK = 4;
     const int gk = attn_grid((L + 16 * NWK * NK - 1) / (16 * NWK * NK), B * H);
-    OD_LAUNCH_DYN((flash_bwd_dkv_kernel<T, HD, NK, NWK, PRE>), dim3(gk), dim3(64 * NWK),
+    OD_LAUNCH_DYN((flash_bwd_dkv_kernel<T, HD, NK, NWK, PRE, VL>), dim3(gk), dim3(64 * NWK),
                   ((Stage<T, HD>::TR ? 2 : 1) * ((2 + 2 * Stage<T, HD>::NT) * Stage<T, HD>::BYTES + 512)), st, (const T*)q, ldq, (const T*)k, ldk,
-                  (const T*)v, ldv, (const T*)dout, lddo, lse, (const float*)delta, (T*)dk, lddk, (T*)dv, lddv, B, H, L, scale);
+                  (const T*)v, ldv, (const T*)dout, lddo, lse, (const float*)delta, (T*)dk, lddk, (T*)dv, lddv, B, H, L, scale, lens);
     constexpr int NWQ = Stage<T, HD>::TR ? OD_ATTN_NW : 4;
     const int gq = attn_grid((L + 16 * NQ * NWQ - 1) / (16 * NQ * NWQ), B * H);
-    OD_LAUNCH_DYN((flash_bwd_dq_kernel<T, HD, NQ, NWQ, PRE>), dim3(gq), dim3(64 * NWQ),
+    OD_LAUNCH_DYN((flash_bwd_dq_kernel<T, HD, NQ, NWQ, PRE, VL>), dim3(gq), dim3(64 * NWQ),
                   ((Stage<T, HD>::TR ? 2 : 1) * ((2 + Stage<T, HD>::NT) * Stage<T, HD>::BYTES)), st_q, (const T*)q, ldq, (const T*)k, ldk,
-                  (const T*)v, ldv, (const T*)dout, lddo, lse, (const float*)delta, (T*)dq, lddq, B, H, L, scale);
+                  (const T*)v, ldv, (const T*)dout, lddo, lse, (const float*)delta, (T*)dq, lddq, B, H, L, scale, lens);
 #if !defined(OD_EMU)
     if (st_q != st) { if (hipEventRecord(aux->join, st_q) != hipSuccess || hipStreamWaitEvent(st, aux->join, 0) != hipSuccess) return OD_ERR_ARG; }
 #endif
@@ -1480,13 +1517,15 @@ extern "C" int od_flash_attn_bwd(int dtype, const void* q, int ldq, const void* 
                                  q_prescaled, nullptr, stream);
 }
 
-extern "C" int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
-                                     int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq,
-                                     void* dk, int lddk, void* dv, int lddv, int B, int H, int L, int hd, float scale, int q_prescaled,
-                                     void* aux, void* stream) {
+namespace {
+template <bool VL>
+int attn_bwd_dispatch(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                      int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                      void* dk, int lddk, void* dv, int lddv, const int* lens, int B, int H, int L, int hd, float scale, int q_prescaled,
+                      void* aux, void* stream) {
     if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 8 || lddk % 8 || lddv % 8) return OD_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
-#define ARGS q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, B, H, L, scale, st, (const AttnAux*)aux
+#define ARGS q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, B, H, L, scale, st, (const AttnAux*)aux, lens
 // Register tiles of the bf16 / hd 64 backward: 16-row tiles per wave.  Per streamed tile every wave pays a fixed budget — its LDS-DMA
 // pieces, the row-wise AND transposed fragment reads of the whole tile pair, the barrier — whatever it owns (removing the in-loop DMA takes
 // 25.5 -> 20.2 ms; deeper tile rings, trimmed loops and 8-wave workgroups change nothing or lose: profiles/r02l_ab_bwd_tile_budget.txt), so
@@ -1507,7 +1546,7 @@ extern "C" int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const vo
 #ifndef OD_BWD128_NQ
 #define OD_BWD128_NQ 2
 #endif
-#define BWD(TT, HDV, NKV, NQV) (q_prescaled ? launch_bwd<TT, HDV, NKV, NQV, true>(ARGS) : launch_bwd<TT, HDV, NKV, NQV, false>(ARGS))
+#define BWD(TT, HDV, NKV, NQV) (q_prescaled ? launch_bwd<TT, HDV, NKV, NQV, true, VL>(ARGS) : launch_bwd<TT, HDV, NKV, NQV, false, VL>(ARGS))
     if (dtype == OD_BF16 && hd == 64) return BWD(bf16_t, 64, OD_BWD_NK, OD_BWD_NQ);
     if (dtype == OD_BF16 && hd == 32) return BWD(bf16_t, 32, 2, 2);
     if (dtype == OD_F32 && hd == 64) return BWD(float, 64, 1, 1);
@@ -1517,4 +1556,24 @@ extern "C" int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const vo
 #undef BWD
 #undef ARGS
     return OD_ERR_UNSUPPORTED;
+}
+}  // namespace
+
+extern "C" int od_flash_attn_bwd_aux(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                                     int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                                     void* dk, int lddk, void* dv, int lddv, int B, int H, int L, int hd, float scale, int q_prescaled,
+                                     void* aux, void* stream) {
+    return attn_bwd_dispatch<false>(dtype, q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, nullptr, B, H, L, hd,
+                                    scale, q_prescaled, aux, stream);
+}
+
+// Ragged batches: sequence b of the padded (B, L) layout is valid for frames < lens[b].  The kernel pair never reads a key at or past lens[b],
+// skips the query rows there (their lse is 0: exp2 of a raw score could overflow) and writes rows >= lens[b] of dq, dk, dv as zeros.
+extern "C" int od_flash_attn_bwd_varlen(int dtype, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o,
+                                        int ldo, const void* dout, int lddo, const float* lse, float* delta, void* dq, int lddq,
+                                        void* dk, int lddk, void* dv, int lddv, const int* lens, int B, int H, int L, int hd, float scale,
+                                        int q_prescaled, void* aux, void* stream) {
+    if (!lens) return OD_ERR_ARG;
+    return attn_bwd_dispatch<true>(dtype, q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, lens, B, H, L, hd,
+                                   scale, q_prescaled, aux, stream);
 }

@@ -114,12 +114,17 @@ struct UHeadG {
 
 // (the LDS sums below are each owned by ONE lane — channel c belongs to lane 0 of group c / cpg — so their order is fixed; only the
 // block-to-global step depends on the order blocks arrive in)
-__global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict__ xt, UHeadW P, const float* __restrict__ dfm,
-                                                        UHeadG G, int E, int L, int U, int nwin, const OdDetTable* __restrict__ det) {
+// VL: as in uhead_fwd_kernel — the mean runs over Lb = lens[b] frames, both convs zero-pad at Lb, windows at or past Lb are skipped; frames >= Lb of
+// xt are never read
+template <bool VL>
+__device__ __forceinline__ void uhead_bwd_body(const float* __restrict__ xt, const UHeadW& P, const float* __restrict__ dfm,
+                                               const UHeadG& G, int E, int L, int U, int nwin, const OdDetTable* __restrict__ det,
+                                               const int* __restrict__ lens) {
     __shared__ UHeadSmem S;
     __shared__ float sdw3[MAXU][3], sdb3[MAXU], sdb4[MAXU], sdw1[MAXU][MAXE], sdb1[MAXU], sdw0[MAXE][3], sdb0[MAXE];
     const int b = blockIdx.y, t = threadIdx.x;
     const int i = t & 31, grp = t >> 5, cpg = U / 8;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     for (int idx = t; idx < MAXU; idx += 256) {
         sdb3[idx] = 0.f; sdb4[idx] = 0.f; sdb1[idx] = 0.f;
         for (int j = 0; j < 3; j++) sdw3[idx][j] = 0.f;
@@ -130,16 +135,17 @@ __global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict_
     float adw4[16];
 #pragma unroll
     for (int q = 0; q < 16; q++) adw4[q] = 0.f;
-    const float invL = 1.0f / (float)L;
+    const float invL = 1.0f / (float)Lb;
 
     for (int wi = 0; wi < UWPB; wi++) {
         const int win = blockIdx.x * UWPB + wi;
         if (win >= nwin) break;
         const int l0 = win * UOWN;
-        uhead_window_fwd(S, xt, P, b, l0, E, L, U, L);
+        if (VL && l0 >= Lb) break;                    // block-uniform
+        uhead_window_fwd(S, xt, P, b, l0, E, L, U, Lb);
         const int f = l0 - 1 + i;
-        const bool inr = (f >= 0 && f < L);
-        const bool own = (i >= 1 && i < UW - 1 && f < L);
+        const bool inr = (f >= 0 && f < Lb);
+        const bool own = (i >= 1 && i < UW - 1 && f < Lb);
         // dz4 for every ext-1 frame
 #pragma unroll
         for (int q = 0; q < MAXU / 8; q++) {
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict_
         __syncthreads();
         // dw4[c][c'] += sum_{owned i} dz4[c][i] * z3[c'][i]
         {
-            const int iend = (L - (l0 - 1)) < (UW - 1) ? (L - (l0 - 1)) : (UW - 1);
+            const int iend = (Lb - (l0 - 1)) < (UW - 1) ? (Lb - (l0 - 1)) : (UW - 1);
 #pragma unroll
             for (int q = 0; q < 16; q++) {
                 const int o = t + 256 * q;
@@ -250,6 +256,16 @@ __global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void uhead_bwd_kernel(const float* __restrict__ xt, UHeadW P, const float* __restrict__ dfm,
+                                                        UHeadG G, int E, int L, int U, int nwin, const OdDetTable* __restrict__ det) {
+    uhead_bwd_body<false>(xt, P, dfm, G, E, L, U, nwin, det, nullptr);
+}
+__global__ __launch_bounds__(256) void uhead_bwd_varlen_kernel(const float* __restrict__ xt, UHeadW P, const float* __restrict__ dfm,
+                                                               UHeadG G, int E, int L, int U, int nwin, const OdDetTable* __restrict__ det,
+                                                               const int* __restrict__ lens) {
+    uhead_bwd_body<true>(xt, P, dfm, G, E, L, U, nwin, det, lens);
+}
+
 // tail: f = fsum/L; fm = f*(1+mod[0:U]) + mod[U:2U]; y = w.fm + b; u = u_scale*softplus(y).  VL: f = fsum/lens[b]
 template <bool VL = false>
 __global__ void uhead_tail_kernel(const float* __restrict__ fsum, const float* __restrict__ mod, const float* __restrict__ w,
@@ -269,21 +285,24 @@ __global__ void uhead_tail_kernel(const float* __restrict__ fsum, const float* _
         u[b] = u_scale * sp;
     }
 }
+template <bool VL = false>
 __global__ void uhead_tail_bwd_kernel(const float* __restrict__ fsum, const float* __restrict__ mod, const float* __restrict__ w,
                                       const float* __restrict__ bo, const float* __restrict__ du, float* __restrict__ dfm,
                                       float* __restrict__ dmod, float* __restrict__ dw, float* __restrict__ dbo,
-                                      int B, int U, int L, float u_scale, const OdDetTable* __restrict__ det) {
+                                      int B, int U, int L, float u_scale, const OdDetTable* __restrict__ det,
+                                      const int* __restrict__ lens = nullptr) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float Lf = (float)(VL ? od_uniform(lens[b]) : L);
     float s = 0.f;
     for (int c = lane; c < U; c += 64) {
-        const float f = fsum[(size_t)b * U + c] / (float)L;
+        const float f = fsum[(size_t)b * U + c] / Lf;
         s += w[c] * (f * (1.f + mod[(size_t)b * 2 * U + c]) + mod[(size_t)b * 2 * U + U + c]);
     }
     s = od_wave_sum(s);
     const float y = s + bo[0];
     const float dy = du[b] * u_scale * od_sigmoid(y);   // d softplus = sigmoid
     for (int c = lane; c < U; c += 64) {
-        const float f = fsum[(size_t)b * U + c] / (float)L;
+        const float f = fsum[(size_t)b * U + c] / Lf;
         const float sc = mod[(size_t)b * 2 * U + c], sh = mod[(size_t)b * 2 * U + U + c];
         const float fm = f * (1.f + sc) + sh;
         od_red_add(det, dw + c, dy * fm);
@@ -304,15 +323,20 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// VL: frames >= Lb = lens[b] of x0 / x1 are not read (they may hold anything); xt there is written as 0 and dsq[b] is the mean over Lb frames
+template <bool VL = false>
 __global__ __launch_bounds__(256) void make_xt_kernel(const float* __restrict__ x0, const float* __restrict__ x1,
                                                       const float* __restrict__ t, float* __restrict__ xt,
-                                                      float* __restrict__ dsq, int EL, int L, const OdDetTable* __restrict__ det) {
+                                                      float* __restrict__ dsq, int EL, int L, const OdDetTable* __restrict__ det,
+                                                      const int* __restrict__ lens = nullptr) {
     __shared__ float sh[4];
     const int b = blockIdx.y;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     const float w = t[b];
     float acc = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < EL; i += gridDim.x * 256) {
         const size_t o = (size_t)b * EL + i;
+        if (VL && (i % L) >= Lb) { xt[o] = 0.f; continue; }
         const float a = x0[o], e = x1[o];
         // torch.lerp: w < 0.5 ? a + w*(e-a) : e - (e-a)*(1-w)
         const float v = w < 0.5f ? a + w * (e - a) : e - (e - a) * (1.f - w);
@@ -321,22 +345,28 @@ __global__ __launch_bounds__(256) void make_xt_kernel(const float* __restrict__ 
         acc += d * d;
     }
     acc = block_sum_256(acc, sh);
-    if (threadIdx.x == 0) od_red_add(det, dsq + b, acc / (float)L);
+    if (threadIdx.x == 0) od_red_add(det, dsq + b, acc / (float)Lb);
 }
 
 // sums[b][0] = S1 = fds(xt - u v, x1), [1] = S2 = fds(v, vt), [2] = dS1/du ; dv = dLoss/dv
+// VL: the sums run over the Lb = lens[b] own frames and are normalised by Lb; frames >= Lb of x1 and v are not read and dv there is written as 0 —
+// from here on the gradient rows of padded frames are exact zeros
+template <bool VL = false>
 __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ xt, const float* __restrict__ x1,
                                                         const float* __restrict__ u, const float* __restrict__ v,
                                                         const float* __restrict__ dsq, float* __restrict__ dv,
                                                         float* __restrict__ sums, int B, int EL, int L, float c0,
-                                                        float osl_w, float del_w, const OdDetTable* __restrict__ det) {
+                                                        float osl_w, float del_w, const OdDetTable* __restrict__ det,
+                                                        const int* __restrict__ lens = nullptr) {
     __shared__ float sh[4];
     const int b = blockIdx.y;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     const float ub = u[b], den = dsq[b] + c0, ut = sqrtf(den);
-    const float k1 = osl_w / ((float)B * den), k2 = del_w / (float)B, invL2 = 2.f / (float)L;
+    const float k1 = osl_w / ((float)B * den), k2 = del_w / (float)B, invL2 = 2.f / (float)Lb;
     float s1 = 0.f, s2 = 0.f, s3 = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < EL; i += gridDim.x * 256) {
         const size_t o = (size_t)b * EL + i;
+        if (VL && (i % L) >= Lb) { dv[o] = 0.f; continue; }
         const float xv = xt[o], e = x1[o], vv = v[o];
         const float r1 = xv - ub * vv - e;          // denoised - x1
         const float r2 = vv - (xv - e) / ut;        // v - v_target
@@ -345,8 +375,8 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     }
     s1 = block_sum_256(s1, sh); s2 = block_sum_256(s2, sh); s3 = block_sum_256(s3, sh);
     if (threadIdx.x == 0) {
-        od_red_add(det, sums + b * 3 + 0, s1 / (float)L);
-        od_red_add(det, sums + b * 3 + 1, s2 / (float)L);
+        od_red_add(det, sums + b * 3 + 0, s1 / (float)Lb);
+        od_red_add(det, sums + b * 3 + 1, s2 / (float)Lb);
         od_red_add(det, sums + b * 3 + 2, s3 * invL2);
     }
 }
@@ -465,6 +495,21 @@ extern "C" int od_uhead_bwd(const float* xt, const float* w0, const float* b0, c
     return 0;
 }
 
+extern "C" int od_uhead_bwd_varlen(const float* xt, const float* w0, const float* b0, const float* w1, const float* b1, const float* w3,
+                                   const float* b3, const float* w4, const float* b4, const float* dfm, float* dw0, float* db0,
+                                   float* dw1, float* db1, float* dw3, float* db3, float* dw4, float* db4, const int* lens, int B, int E,
+                                   int L, int U, void* stream) {
+    if (U > MAXU || U % 8 || E > MAXE) return OD_ERR_UNSUPPORTED;
+    if (!lens) return OD_ERR_ARG;
+    const int nwin = (L + UOWN - 1) / UOWN;
+    UHeadW P{w0, b0, w1, b1, w3, b3, w4, b4};
+    UHeadG G{dw0, db0, dw1, db1, dw3, db3, dw4, db4};
+    OD_LAUNCH(uhead_bwd_varlen_kernel, dim3((nwin + UWPB - 1) / UWPB, B), dim3(256), 0, (hipStream_t)stream, xt, P, dfm, G, E, L, U, nwin,
+              od_det_active(), lens);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int od_uhead_tail(const float* fsum, const float* mod, const float* w_out, const float* b_out, float* u, int B, int U,
                              int L, float u_scale, void* stream) {
     OD_LAUNCH(uhead_tail_kernel<>, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, u, B, U, L, u_scale);
@@ -483,8 +528,18 @@ extern "C" int od_uhead_tail_varlen(const float* fsum, const float* mod, const f
 extern "C" int od_uhead_tail_bwd(const float* fsum, const float* mod, const float* w_out, const float* b_out, const float* du,
                                  float* dfm, float* dmod, float* dw_out, float* db_out, int B, int U, int L, float u_scale,
                                  void* stream) {
-    OD_LAUNCH(uhead_tail_bwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, du, dfm, dmod, dw_out,
+    OD_LAUNCH(uhead_tail_bwd_kernel<>, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, du, dfm, dmod, dw_out,
               db_out, B, U, L, u_scale, od_det_active());
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_uhead_tail_bwd_varlen(const float* fsum, const float* mod, const float* w_out, const float* b_out, const float* du,
+                                        float* dfm, float* dmod, float* dw_out, float* db_out, const int* lens, int B, int U, int L,
+                                        float u_scale, void* stream) {
+    if (!lens) return OD_ERR_ARG;
+    OD_LAUNCH(uhead_tail_bwd_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, fsum, mod, w_out, b_out, du, dfm, dmod, dw_out,
+              db_out, B, U, L, u_scale, od_det_active(), lens);
     OD_CHECK_LAUNCH();
     return 0;
 }
@@ -492,7 +547,19 @@ extern "C" int od_uhead_tail_bwd(const float* fsum, const float* mod, const floa
 extern "C" int od_make_xt(const float* x0, const float* x1, const float* t, float* xt, float* dsq, int B, int E, int L, void* stream) {
     const int EL = E * L;
     int gx = (EL + 255) / 256; if (gx > 256) gx = 256;
-    OD_LAUNCH(make_xt_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x1, t, xt, dsq, EL, L, od_det_active());
+    OD_LAUNCH(make_xt_kernel<>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x1, t, xt, dsq, EL, L, od_det_active());
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+// blocks per sequence of the varlen loss kernels: od_make_xt's and od_loss_grad's own choice
+static inline int loss_grid_x(int EL) { const int g = (EL + 255) / 256; return g > 256 ? 256 : g; }
+
+extern "C" int od_make_xt_varlen(const float* x0, const float* x1, const float* t, float* xt, float* dsq, const int* lens, int B, int E,
+                                 int L, void* stream) {
+    if (!lens) return OD_ERR_ARG;
+    const int EL = E * L, gx = loss_grid_x(EL);
+    OD_LAUNCH(make_xt_kernel<true>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x0, x1, t, xt, dsq, EL, L, od_det_active(), lens);
     OD_CHECK_LAUNCH();
     return 0;
 }
@@ -501,7 +568,17 @@ extern "C" int od_loss_grad(const float* xt, const float* x1, const float* u, co
                             float* sums, int B, int E, int L, float c0, float osl_w, float del_w, void* stream) {
     const int EL = E * L;
     int gx = (EL + 255) / 256; if (gx > 256) gx = 256;
-    OD_LAUNCH(loss_grad_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, xt, x1, u, v, dsq, dv, sums, B, EL, L, c0, osl_w, del_w, od_det_active());
+    OD_LAUNCH(loss_grad_kernel<>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, xt, x1, u, v, dsq, dv, sums, B, EL, L, c0, osl_w, del_w, od_det_active());
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_loss_grad_varlen(const float* xt, const float* x1, const float* u, const float* v, const float* dsq, float* dv,
+                                   float* sums, const int* lens, int B, int E, int L, float c0, float osl_w, float del_w, void* stream) {
+    if (!lens) return OD_ERR_ARG;
+    const int EL = E * L, gx = loss_grid_x(EL);
+    OD_LAUNCH(loss_grad_kernel<true>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, xt, x1, u, v, dsq, dv, sums, B, EL, L, c0, osl_w, del_w,
+              od_det_active(), lens);
     OD_CHECK_LAUNCH();
     return 0;
 }

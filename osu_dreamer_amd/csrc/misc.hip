@@ -211,18 +211,20 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, in
 // backward: dx[l] = sum_j w[j] dy[l - j + R];  dw[j] += sum_l dy[l] x[l + j - R];  db += sum_l dy[l]
 // The per-channel weight/bias sums are reduced across the block in LDS before they touch global
 // atomics (one atomic per (channel, tap) per block instead of per thread).
+// VL: taps of x and dy at frames >= Lb = lens[b] read as zero (selected: the rows are never loaded) and dx there is written as zero.
 constexpr int DW_RUN_BWD = 64;
-template <class T, int KS>
+template <class T, int KS, bool VL = false>
 __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w,
                                                          const T* __restrict__ dy, int lddy, T* __restrict__ dx, int lddx,
                                                          float* __restrict__ dw, float* __restrict__ db, int L, int C,
-                                                         const OdDetTable* __restrict__ det) {
+                                                         const OdDetTable* __restrict__ det, const int* __restrict__ lens = nullptr) {
     constexpr int R = KS / 2;
     // fixed point (od_lds_fix_add): the block's sums do not depend on the order its threads arrive in.  C <= 1024 at k <= 5, 512 above (launcher)
     __shared__ long long red[(KS <= 5 ? 1024 : 512) * (KS + 1)];
     __shared__ int s_bad;
     const int cg = C / 8;
     const int b = blockIdx.y;
+    const int Lb = VL ? od_uniform(lens[b]) : L;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const int cgi = (int)(t % cg);
     const long run = t / cg;
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ x
 #pragma unroll
         for (int j = 0; j < KS - 1; j++) {
             const int l = l0 - R + j;
-            if (l >= 0 && l < L) { od_ld8(xb + (size_t)l * ldx, wx[j]); od_ld8(yb + (size_t)l * lddy, wy[j]); }
+            if (l >= 0 && l < Lb) { od_ld8(xb + (size_t)l * ldx, wx[j]); od_ld8(yb + (size_t)l * lddy, wy[j]); }
             else {
 #pragma unroll
                 for (int k = 0; k < 8; k++) { wx[j][k] = 0.f; wy[j][k] = 0.f; }
@@ -260,7 +262,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ x
         typedef typename std::conditional<sizeof(T) == 2, u32x4, f32x4>::type row_t;      // 8 channels as loaded (bf16: one 16-byte word)
         row_t px[DW_PF][sizeof(T) == 2 ? 1 : 2], py[DW_PF][sizeof(T) == 2 ? 1 : 2];
         auto fetch = [&](int ln, int slot) {
-            if (ln < L) {
+            if (ln < Lb) {
 #pragma unroll
                 for (int h2 = 0; h2 < (sizeof(T) == 2 ? 1 : 2); h2++) {
                     px[slot][h2] = *(const row_t*)(xb + (size_t)ln * ldx + h2 * 4);
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ x
                 // window slot j holds frame l - R + j; dx[l] += w[jj] * dy[l - jj + R]  ->  slot = 2R - jj
 #pragma unroll
                 for (int jj = 0; jj < KS; jj++) sacc += wv[k][jj] * wy[KS - 1 - jj][k];
-                o[k] = sacc;
+                o[k] = (VL && l >= Lb) ? 0.f : sacc;
                 const float gy = wy[R][k];     // dy[l]
                 adb[k] += gy;
 #pragma unroll
@@ -601,6 +603,24 @@ extern "C" int od_dwconv_bwd(int dtype, const void* x, int ldx, const float* w, 
     else if (ksize == 7 && C <= 512) DISPATCH_T(dtype, OD_LAUNCH((dwconv_bwd_kernel<T_, 7>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, w, (const T_*)dy, lddy, (T_*)dx, lddx, dw, db, L, C, od_det_active()));
     else if (ksize == 9 && C <= 512) DISPATCH_T(dtype, OD_LAUNCH((dwconv_bwd_kernel<T_, 9>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, w, (const T_*)dy, lddy, (T_*)dx, lddx, dw, db, L, C, od_det_active()));
     else return OD_ERR_UNSUPPORTED;
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_dwconv_bwd_varlen(int dtype, const void* x, int ldx, const float* w, const void* dy, int lddy, void* dx, int lddx,
+                                    float* dw, float* db, const int* lens, int B, int L, int C, int ksize, void* stream) {
+    if (C % 8 || ldx % 8 || lddy % 8 || lddx % 8) return OD_ERR_ALIGN;
+    if (C > 1024 || (ksize > 5 && C > 512)) return OD_ERR_UNSUPPORTED;
+    if (!lens) return OD_ERR_ARG;
+    const long threads = (long)(C / 8) * ((L + DW_RUN_BWD - 1) / DW_RUN_BWD);
+    dim3 grid((unsigned)((threads + 255) / 256), B);
+#define DWB_GO(KS_) DISPATCH_T(dtype, OD_LAUNCH((dwconv_bwd_kernel<T_, KS_, true>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)x, ldx, w, (const T_*)dy, lddy, (T_*)dx, lddx, dw, db, L, C, od_det_active(), lens))
+    if (ksize == 5) DWB_GO(5);
+    else if (ksize == 3) DWB_GO(3);
+    else if (ksize == 7) DWB_GO(7);
+    else if (ksize == 9) DWB_GO(9);
+    else return OD_ERR_UNSUPPORTED;
+#undef DWB_GO
     OD_CHECK_LAUNCH();
     return 0;
 }

@@ -60,6 +60,29 @@ class LatentBatch(NamedTuple):
     labels: torch.Tensor   # (NUM_LABELS,)
 
 
+class RaggedLatentBatch(NamedTuple):
+    """N whole maps of different lengths, zero-padded to a common Lpad: map b is valid for frames < lengths[b].  What
+    `LatentDataModule(seq_len=None, batch_size=N > 1)` collates and `DiffusionTrainer.training_step` accepts beside the 4-tuple."""
+    h: torch.Tensor        # (N, A, Lpad)
+    z: torch.Tensor        # (N, E, Lpad)
+    s: torch.Tensor        # (N, S)
+    labels: torch.Tensor   # (N, NUM_LABELS)
+    lengths: torch.Tensor  # (N,) int64, on the host
+
+
+def collate_ragged(samples: List[LatentBatch], pad_multiple: int = 64) -> RaggedLatentBatch:
+    """Whole maps -> one RaggedLatentBatch, zero-padded to the longest map rounded up to `pad_multiple` (few distinct padded lengths: the
+    engine keeps one workspace per (N, Lpad))."""
+    lens = [int(b.z.size(-1)) for b in samples]
+    Lpad = (max(lens) + pad_multiple - 1) // pad_multiple * pad_multiple
+    h = torch.zeros(len(samples), samples[0].h.size(0), Lpad)
+    z = torch.zeros(len(samples), samples[0].z.size(0), Lpad)
+    for i, (b, n) in enumerate(zip(samples, lens)):
+        h[i, :, :n], z[i, :, :n] = b.h[..., :n], b.z
+    return RaggedLatentBatch(h, z, torch.stack([b.s for b in samples]), torch.stack([b.labels for b in samples]),
+                             torch.tensor(lens, dtype=torch.int64))
+
+
 def load_latents(latent_file: Path) -> LatentBatch:
     """`<map>.latent.npz` {z, s, labels} + sibling `h.npy` (latent.py:74-80)."""
     with np.load(latent_file) as d:
@@ -111,9 +134,10 @@ def hold_out_mapsets(data_dir: Path, pattern: str, max_val_count: int, max_val_f
 
 class LatentDataset(IterableDataset):
     def __init__(self, mapsets: List[Path], seq_len: Optional[int] = None, shuffle_buffer_size: int = 1,
-                 max_per_map: int = -1, rank: int = 0, world_size: int = 1):
+                 max_per_map: int = -1, rank: int = 0, world_size: int = 1, max_len: Optional[int] = None):
+        """`max_len` (whole maps, seq_len None, only): a map longer than that contributes one random window of max_len frames."""
         super().__init__()
-        self.mapsets, self.seq_len = mapsets, seq_len
+        self.mapsets, self.seq_len, self.max_len = mapsets, seq_len, max_len
         self.shuffle_buffer_size = shuffle_buffer_size
         self.max_per_map = max_per_map if max_per_map > 0 else float("inf")
         self.rank, self.world_size = rank, world_size
@@ -148,6 +172,10 @@ class LatentDataset(IterableDataset):
     def make_samples(self, latent_file: Path) -> Iterator[LatentBatch]:
         h, z, s, labels = load_latents(latent_file)
         if self.seq_len is None:
+            L = z.size(-1)
+            if self.max_len is not None and L > self.max_len:
+                i = int(torch.randint(0, L - self.max_len + 1, ()).item())
+                h, z = h[..., i:i + self.max_len].clone(), z[..., i:i + self.max_len].clone()
             yield LatentBatch(h, z, s, labels)
             return
         end = z.size(-1) - self.seq_len + 1
@@ -161,19 +189,32 @@ class LatentDataset(IterableDataset):
 
 
 class LatentDataModule:
-    """Same constructor keys as the reference's LatentDataModule (they are the YAML `data:` block)."""
+    """Same constructor keys as the reference's LatentDataModule (they are the YAML `data:` block), plus `max_len` and `pad_multiple` for
+    ragged training: with `seq_len: null` and `batch_size` N > 1 the training loader collates N whole maps into one `RaggedLatentBatch`,
+    zero-padded to the longest map rounded up to `pad_multiple`; a map longer than `max_len` contributes a random window of `max_len`
+    frames, which bounds the step's memory.  With an integer `seq_len` nothing changes."""
 
-    def __init__(self, batch_size: int, seq_len: int, num_workers: int, max_val_count: int = 512,
+    def __init__(self, batch_size: int, seq_len: Optional[int], num_workers: int, max_val_count: int = 512,
                  max_val_frac: float = .3, data_path: str = "./data", shuffle_buffer_size: int = 1,
-                 max_per_map: int = -1, rank: int = 0, world_size: int = 1):
+                 max_per_map: int = -1, rank: int = 0, world_size: int = 1, max_len: Optional[int] = None, pad_multiple: int = 64):
         self.batch_size, self.seq_len, self.num_workers = batch_size, seq_len, num_workers
+        if seq_len is not None and max_len is not None:
+            raise ValueError("data.max_len bounds whole maps: it applies with seq_len: null only")
+        if max_len is not None and max_len < 1 or pad_multiple < 1:
+            raise ValueError(f"invalid {max_len=} / {pad_multiple=}")
+        self.max_len, self.pad_multiple = max_len, int(pad_multiple)
+        self.ragged = seq_len is None and batch_size > 1
         train, val = hold_out_mapsets(Path(data_path), "*.latent.npz", max_val_count, max_val_frac)
-        self.train_set = LatentDataset(train, seq_len, shuffle_buffer_size, max_per_map, rank, world_size)
+        self.train_set = LatentDataset(train, seq_len, shuffle_buffer_size, max_per_map, rank, world_size, max_len=max_len)
         self.val_set = LatentDataset(val)
 
     def train_dataloader(self):
+        collate = {"collate_fn": self._collate} if self.ragged else {}
         return DataLoader(self.train_set, batch_size=self.batch_size, num_workers=self.num_workers, pin_memory=True,
-                          persistent_workers=self.num_workers > 0, drop_last=True)
+                          persistent_workers=self.num_workers > 0, drop_last=True, **collate)
+
+    def _collate(self, samples):
+        return collate_ragged(samples, self.pad_multiple)
 
     def val_dataloader(self):
         return DataLoader(self.val_set, batch_size=1, num_workers=min(1, self.num_workers), pin_memory=True,

@@ -173,14 +173,16 @@ class DenoiserEngine:
     # ------------------------------------------------------------------ plan / workspace
     def plan(self, B: int, L: int, Ba: int, dtype: torch.dtype, train: bool, x3: bool = False, lens=None, offs=None):
         """`x3`: run the fp32 forward's MFMA products as 3 bf16 MFMAs (OD_F32X3; no-grad paths only).
-        `lens` (B ints, 1 <= lens[b] <= L; no-grad only): varlen — row b of the padded (B, L) layout is valid for frames < lens[b], and
-        `pred` runs the varlen kernels wherever frames mix (attention, depthwise convs, the u-head's convs and mean).  `offs` (G + 1 ints):
+        `lens` (B ints, 1 <= lens[b] <= L): varlen — row b of the padded (B, L) layout is valid for frames < lens[b], and `pred` runs the
+        varlen kernels wherever frames mix (attention, depthwise convs, the u-head's convs and mean).  With `train` the forward stores its
+        activations as the dense one does and `backward` runs the varlen backward of those same kernels; every other backward kernel is row-wise
+        and relies on the zero-row invariant: the caller hands `backward` a dv whose padded frames are exact zeros and an xt and
+        audio whose padded frames are finite.  `offs` (G + 1 ints):
         the song boundaries over the rows, for the per-song sampler step size.  Both live in plan-owned device int32 buffers, refreshed by a
         stream-ordered copy on every call: the lengths are not part of the plan key, so a captured sampler graph of the same shape replays."""
         dev = self.model.arena.data.device
         assert not (x3 and train), "the f32x3 product exists for the forward kernels only"
         varlen = lens is not None
-        assert not (varlen and train), "the varlen forward exists for no-grad paths only"
         x3 = bool(x3 and dtype == torch.float32)
         ngroups = len(offs) - 1 if offs is not None else 0
         key = (B, L, Ba, dtype, train, dev, x3, getattr(self.model, "attn_dtype", None), varlen, ngroups)
@@ -213,6 +215,9 @@ class DenoiserEngine:
                               f"{self.hd}) runs its attention in {dtype}")
                 self._warned_f16_fallback = True
             self.attn_f16 = False
+        if varlen and train and self.attn_f16:
+            raise NotImplementedError("ragged training has no half-operand attention (attn_dtype = float16 runs the fused backward, which has no "
+                                      "varlen form): train ragged batches with attn_dtype = None")
         return self.ws
 
     def buf(self, name, shape, dtype=None):
@@ -373,7 +378,7 @@ class DenoiserEngine:
         consecutive key blocks start (L / 64) / (CUs per XCD) tiles apart.)
         OD_ATTN_BWD_FUSED=0 / 1 forces the two-kernel / the fused path.  head_dim 32 and 128 have no fused form: the kernel pair at every L."""
         import os
-        if self.dtype != torch.bfloat16 or self.hd != 64:
+        if self.dtype != torch.bfloat16 or self.hd != 64 or self.varlen:     # (ragged plans: the kernel pair at every L, whatever the switch says)
             return False
         if self.attn_f16:
             return True                     # the half-operand backward exists as the fused kernel only
@@ -410,8 +415,13 @@ class DenoiserEngine:
                 with torch.cuda.device(qk.device):          # the side stream and its events belong to the tensors' device
                     self._attn_aux = ops.AttnAux()          # side stream + events: the dQ kernel runs beside the dK/dV kernel
                 self._attn_aux.device = qk.device
-            ops.flash_attn_bwd(qk[:, :dh], qk[:, dh:], qkv[:, 2 * dh:], y, dy, lse, delta, dqk[:, :dh], dqk[:, dh:],
-                               dqkv[:, 2 * dh:], self.B, self.H, self.L, self.hd, scale, q_prescaled=True, aux=self._attn_aux)
+            if self.varlen:       # rows >= lens[b] of dqk and of dqkv's v columns come back as zeros: d.qkv is reused from layer to layer
+                ops.flash_attn_bwd_varlen(qk[:, :dh], qk[:, dh:], qkv[:, 2 * dh:], y, dy, lse, delta, dqk[:, :dh], dqk[:, dh:],
+                                          dqkv[:, 2 * dh:], self.ws.t["vl.lens"], self.B, self.H, self.L, self.hd, scale, q_prescaled=True,
+                                          aux=self._attn_aux)
+            else:
+                ops.flash_attn_bwd(qk[:, :dh], qk[:, dh:], qkv[:, 2 * dh:], y, dy, lse, delta, dqk[:, :dh], dqk[:, dh:],
+                                   dqkv[:, 2 * dh:], self.B, self.H, self.L, self.hd, scale, q_prescaled=True, aux=self._attn_aux)
         if not core_only:
             ops.qk_norm_rope_bwd(qkv, wq, wk, t["rope"], dqk, dqkv, gq, gk, self.B, self.L, self.H, self.hd, FP32_EPS, q_scale=self.q_scale)
 
@@ -442,7 +452,10 @@ class DenoiserEngine:
     def backward(self, xt: torch.Tensor, style: torch.Tensor, du: torch.Tensor, dv: torch.Tensor, reducer=None):
         """Accumulate dLoss/dparam into the arena's grad buffer given dLoss/du [B], dLoss/dv (B,E,L).
         Mirrors `pred` in reverse.  `reducer.layer_done(i)` (if given) is told when a layer's
-        gradients are final so their all-reduce can overlap the rest of backward."""
+        gradients are final so their all-reduce can overlap the rest of backward.
+        Ragged plans (plan(..., train=True, lens=...)): dv must be exactly zero at frames >= lens[b] (od_loss_grad_varlen writes it so).  The
+        kernels where frames mix run their varlen backward; the row-wise kernels and the GEMMs turn a zero gradient row into zero rows and add
+        nothing to a weight, bias or FiLM sum for it, as long as the stored activations of those rows are finite."""
         assert self.train
         B, L, M, D, dh, Hf, Hp, A = self.B, self.L, self.M, self.D, self.dh, self.Hf, self.Hp, self.A
         f32 = torch.float32
@@ -468,9 +481,15 @@ class DenoiserEngine:
                                     self.G("proj_out.weight"), self.G("proj_out.bias"), B, L)
         # distance head
         dfm, dmod = self.buf("d.fm", (B, self.U), f32), self.buf("d.mod", (B, 2 * self.U), f32)
-        ops.uhead_tail_bwd(self.ws.t["fsum"], self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), du,
-                           dfm, dmod, self.G("u_out.weight"), self.G("u_out.bias"), L, self.model.u_scale)
-        ops.uhead_bwd(xt, self._uhead_w(), dfm, self._uhead_w(grads=True), self.U)
+        if self.varlen:
+            lens = self.ws.t["vl.lens"]
+            ops.uhead_tail_bwd_varlen(self.ws.t["fsum"], self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), du,
+                                      dfm, dmod, self.G("u_out.weight"), self.G("u_out.bias"), lens, L, self.model.u_scale)
+            ops.uhead_bwd_varlen(xt, self._uhead_w(), dfm, self._uhead_w(grads=True), lens, self.U)
+        else:
+            ops.uhead_tail_bwd(self.ws.t["fsum"], self.ws.t["umod"], self.P("u_out.weight"), self.P("u_out.bias"), du,
+                               dfm, dmod, self.G("u_out.weight"), self.G("u_out.bias"), L, self.model.u_scale)
+            ops.uhead_bwd(xt, self._uhead_w(), dfm, self._uhead_w(grads=True), self.U)
         ops.linear_small_bwd(cg, self.P("u_mod.weight"), None, dmod, self.buf("d.lin_pre_umod", (B, 2 * self.U), f32),
                              self.G("u_mod.weight"), self.G("u_mod.bias"), dcg, False, OD_ACT_NONE)
         self._det_flush_segment("tail")
@@ -497,8 +516,12 @@ class DenoiserEngine:
             ops.gemm_tn(dvg, hdw, gw, n_cols=2 * Hp, k_cols=D, dbias=gb, n_block=Hp, n_valid=Hf)
             if self.radius > 0:
                 self.plain_gemm(dvg, self.W(p + "ffn.proj_vg.1", T=True), None, dtmp)
-                ops.dwconv_bwd(t[f"h2.{i}"], self.P(p + "ffn.proj_vg.0.weight"), dtmp, dbr,
-                               self.G(p + "ffn.proj_vg.0.weight"), self.G(p + "ffn.proj_vg.0.bias"), B, L, self.ksize)
+                if self.varlen:       # h2's padded rows are finite but not zero: the conv's weight gradient must not see them
+                    ops.dwconv_bwd_varlen(t[f"h2.{i}"], self.P(p + "ffn.proj_vg.0.weight"), dtmp, dbr, self.G(p + "ffn.proj_vg.0.weight"),
+                                          self.G(p + "ffn.proj_vg.0.bias"), self.ws.t["vl.lens"], B, L, self.ksize)
+                else:
+                    ops.dwconv_bwd(t[f"h2.{i}"], self.P(p + "ffn.proj_vg.0.weight"), dtmp, dbr,
+                                   self.G(p + "ffn.proj_vg.0.weight"), self.G(p + "ffn.proj_vg.0.bias"), B, L, self.ksize)
             else:
                 self.plain_gemm(dvg, self.W(p + "ffn.proj_vg.1", T=True), None, dbr)
             ops.rmsnorm_film_bwd(t[f"x_mid.{i}"], t[f"inv3.{i}"], ssg2, dbr, dx, dssg2, B, L)

@@ -37,7 +37,7 @@ import torch
 import yaml
 
 from . import _lib, launch
-from .data import LatentDataModule
+from .data import LatentDataModule, RaggedLatentBatch
 from .lr_schedule import LRScheduleArgs
 from .model import BackboneArgs, DiffusionModelArgs
 from .train import DiffusionTrainer
@@ -115,6 +115,8 @@ class Trainer:
         return torch.autocast(device.type, enabled=False)
 
     def _to(self, batch, device):
+        if isinstance(batch, RaggedLatentBatch):          # the lengths stay on the host: the engine plans with them
+            return RaggedLatentBatch(*(t.to(device, non_blocking=True) for t in batch[:4]), batch.lengths)
         return tuple(t.to(device, non_blocking=True) for t in batch)
 
     def save_checkpoint(self, path, module, opt, sched):
@@ -305,6 +307,15 @@ def build_from_config(cfg: Dict[str, Any]):
     return module, Trainer(**t)
 
 
+def refuse_ragged_data_parallel(cfg: Dict[str, Any], devices: int):
+    """Ragged training (data.seq_len: null) is implemented and tested for one device."""
+    data = cfg.get("data") or {}
+    if devices > 1 and "seq_len" in data and data["seq_len"] is None:
+        raise RuntimeError(f"ragged training (data.seq_len: null) runs on one device, got trainer.devices={devices}: data-parallel ragged "
+                           "steps are not implemented.  Train whole maps with trainer.devices: 1, or fixed windows (an integer "
+                           "data.seq_len) on several devices")
+
+
 def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
     """begin a training run for the diffusion model (reference: scripts/fit_denoiser.py:17-32)."""
     with open(config) as f:
@@ -315,6 +326,7 @@ def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, 
     if cfg.get("seed_everything") not in (None, False):
         seed_everything(cfg["seed_everything"])
     devices = launch.parse_devices(cfg.get("trainer", {}).get("devices", 1))
+    refuse_ragged_data_parallel(cfg, devices)
     if devices > 1 and launch.world_from_env() is None:
         # this function runs INSIDE a rank; only the CLI (main(), below) starts ranks, because that has to happen in a process
         # that never touches the GPU
@@ -420,7 +432,9 @@ def main(argv=None):
         return
     if a.cmd == "fit-denoiser":
         with open(a.config) as fh:
-            devices = launch.parse_devices((yaml.safe_load(fh).get("trainer") or {}).get("devices", 1))
+            cfg = yaml.safe_load(fh)
+        devices = launch.parse_devices((cfg.get("trainer") or {}).get("devices", 1))
+        refuse_ragged_data_parallel(cfg, devices)       # before any rank is started
         # trainer.devices N > 1: this process only starts the N ranks (children; nothing here has touched the GPU)
         rc = launch.spawn_ranks_if_needed(devices, ["fit-denoiser", "-c", a.config] + (["--ckpt-path", a.ckpt_path] if a.ckpt_path else []),
                                           module="osu_dreamer_amd")

@@ -270,16 +270,21 @@ class DiffusionModel(nn.Module):
 
     # ---- forward (model.py:105-114) --------------------------------------------------
     def forward(self, audio: torch.Tensor, style: torch.Tensor, xt: torch.Tensor, *, lengths=None):
-        """`lengths` (B ints, optional; no-grad only): row b of the batch is a sequence of lengths[b] frames zero-padded to L — attention, the
+        """`lengths` (B ints, optional): row b of the batch is a sequence of lengths[b] frames zero-padded to L — attention, the
         depthwise convs and the u-head's mean see its own frames only, and frames >= lengths[b] of v come back as zero.  `audio` is then
-        (B, A, L), or (1, A, L) when every row has the same audio."""
+        (B, A, L), or (1, A, L) when every row has the same audio.  With grad enabled and the module in training mode the call is
+        differentiable (the ragged training forward): the padding of audio and xt is not read (it is replaced by zeros), and the gradient that
+        arrives for v's padded frames is dropped.  In eval mode with grad enabled it raises, as it always did: an inference call that forgot
+        torch.no_grad() should not silently record a training step's activations."""
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if lengths is not None:
-            if grad:
-                raise RuntimeError("forward(..., lengths=...) has no backward: call it under torch.no_grad()")
+        if lengths is not None and not grad:
             return self._forward_nograd(audio, style, xt, lengths=lengths)
+        if lengths is not None and not self.training:
+            raise RuntimeError("forward(..., lengths=...) has no backward in eval mode: call it under torch.no_grad(), or put the module in "
+                               "training mode (model.train()) for the ragged training forward")
         if grad:
-            return _DenoiserFn.apply(self, audio, style, xt, *self.parameters())
+            lens = None if lengths is None else [int(n) for n in torch.as_tensor(lengths).tolist()]
+            return _DenoiserFn.apply(self, lens, audio, style, xt, *self.parameters())
         return self._forward_nograd(audio, style, xt)
 
     def _forward_nograd(self, audio, style, xt, lengths=None):
@@ -417,24 +422,41 @@ class DiffusionModel(nn.Module):
                 step()
 
 
+def valid_frames(lens, L: int, device) -> torch.Tensor:
+    """(B, 1, L) bool: frame l of row b lies inside the sequence (l < lens[b])."""
+    n = torch.as_tensor(lens, dtype=torch.int64).to(device)
+    return (torch.arange(L, device=device)[None, :] < n[:, None])[:, None, :]
+
+
+def zero_padding(x: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+    """A copy of (B, C, L) `x` with the frames outside `valid` as zeros — selected, so NaN or Inf there does not survive."""
+    return torch.where(valid, x, torch.zeros((), dtype=x.dtype, device=x.device)).contiguous()
+
+
 class _DenoiserFn(torch.autograd.Function):
     """Autograd glue for `DiffusionModel.forward`: one node for the whole network.  Parameter
     gradients are accumulated by the backward kernels directly into `arena.grad` (which every
     parameter's .grad aliases), so None is returned for them."""
 
     @staticmethod
-    def forward(ctx, model: DiffusionModel, audio, style, xt, *params):
+    def forward(ctx, model: DiffusionModel, lens, audio, style, xt, *params):
         audio, style, xt = model._f32c(audio), model._f32c(style), model._f32c(xt)
         B, _, L = xt.shape
         if audio.shape[0] == 1 and B > 1:
             audio = audio.expand(B, -1, -1).contiguous()   # training never broadcasts (data/modules/latent.py:55-62)
         eng, dt = model.engine, model._dtype()
         eng.pack_weights(dt, train=True)
-        eng.plan(B, L, audio.shape[0], dt, train=True)
+        eng.plan(B, L, audio.shape[0], dt, train=True, lens=lens)
+        ctx.valid = None
+        if lens is not None:      # ragged: the padded frames of the inputs are replaced by zeros (the backward needs finite activations there)
+            ctx.valid = valid_frames(lens, L, xt.device)
+            audio, xt = zero_padding(audio, ctx.valid), zero_padding(xt, ctx.valid)
         eng.conditioning(audio, style)
         u = torch.empty(B, dtype=torch.float32, device=xt.device)
         v = torch.empty_like(xt)
         eng.pred(xt, u, v)
+        if lens is not None:
+            v = zero_padding(v, ctx.valid)
         ctx.model, ctx.xt, ctx.style = model, xt, style
         ctx.nparams = len(params)
         return u, v
@@ -446,5 +468,7 @@ class _DenoiserFn(torch.autograd.Function):
         B = ctx.xt.shape[0]
         du = torch.zeros(B, device=ctx.xt.device) if du is None else du.to(torch.float32).contiguous()
         dv = torch.zeros_like(ctx.xt) if dv is None else dv.to(torch.float32).contiguous()
+        if ctx.valid is not None:
+            dv = zero_padding(dv, ctx.valid)               # the zero-row invariant of the ragged backward starts here
         model.engine.backward(ctx.xt, ctx.style, du, dv, reducer=getattr(model, "_reducer", None))
-        return (None, None, None, None) + (None,) * ctx.nparams
+        return (None, None, None, None, None) + (None,) * ctx.nparams

@@ -302,6 +302,16 @@ def flash_attn_bwd(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, L, hd, scale, q
                                      B, H, L, hd, scale, int(q_prescaled), aux.handle if aux is not None else None, _stream(q))
 
 
+def flash_attn_bwd_varlen(q, k, v, o, do, lse, delta, dq, dk, dv, lens, B, H, L, hd, scale, q_prescaled=False, aux=None):
+    """flash_attn_bwd per sequence (lens: device int32 [B]): rows >= lens[b] of q, k, v, do are never used and rows >= lens[b] of
+    dq, dk, dv come back as exact zeros."""
+    _f32(lse, delta)
+    _i32(lens)
+    _lib.lib().od_flash_attn_bwd_varlen(dt_code(q.dtype), _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), _p(o), _ld(o), _p(do),
+                                        _ld(do), _p(lse), _p(delta), _p(dq), _ld(dq), _p(dk), _ld(dk), _p(dv), _ld(dv), _p(lens),
+                                        B, H, L, hd, scale, int(q_prescaled), aux.handle if aux is not None else None, _stream(q))
+
+
 class FusedAttnBwdWorkspace:
     """Caller-owned device memory of od_flash_attn_bwd_fused for one (B, H, L): control block + chain flags (zeroed once here; every call
     leaves them zero), the start values (-lse', -delta) and the running dQ tiles.  One instance serves every layer of a step (same stream)."""
@@ -374,6 +384,15 @@ def dwconv_bwd(x, w, dy, dx, dw, db, B, L, ksize):
                              B, L, C, ksize, _stream(x))
 
 
+def dwconv_bwd_varlen(x, w, dy, dx, dw, db, lens, B, L, ksize):
+    """dwconv_bwd per sequence of valid length lens[b] (device int32 [B]); frames >= lens[b] of dx come back as 0."""
+    C = x.shape[1]
+    _f32(w, dw, db)
+    _i32(lens)
+    _lib.lib().od_dwconv_bwd_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(dy), _ld(dy), _p(dx), _ld(dx), _p(dw), _p(db),
+                                    _p(lens), B, L, C, ksize, _stream(x))
+
+
 def scale_channels(x, scale, B, L):
     """x[(b, l), c] *= scale[b, c] in place (Dropout1d's channel mask; also its backward)."""
     _f32(scale)
@@ -430,6 +449,13 @@ def uhead_bwd(xt, w, dfm, g, U):
     _lib.lib().od_uhead_bwd(_p(xt), *[_p(t) for t in w], _p(dfm), *[_p(t) for t in g], B, E, L, U, _stream(xt))
 
 
+def uhead_bwd_varlen(xt, w, dfm, g, lens, U):
+    B, E, L = xt.shape
+    _f32(xt, dfm, *w, *g)
+    _i32(lens)
+    _lib.lib().od_uhead_bwd_varlen(_p(xt), *[_p(t) for t in w], _p(dfm), *[_p(t) for t in g], _p(lens), B, E, L, U, _stream(xt))
+
+
 def uhead_tail(fsum, mod, w_out, b_out, u, L, u_scale):
     B, U = fsum.shape
     _f32(fsum, mod, w_out, b_out, u)
@@ -450,6 +476,14 @@ def uhead_tail_bwd(fsum, mod, w_out, b_out, du, dfm, dmod, dw_out, db_out, L, u_
                                  _p(db_out), B, U, L, u_scale, _stream(fsum))
 
 
+def uhead_tail_bwd_varlen(fsum, mod, w_out, b_out, du, dfm, dmod, dw_out, db_out, lens, L, u_scale):
+    B, U = fsum.shape
+    _f32(fsum, mod, w_out, b_out, du, dfm, dmod, dw_out, db_out)
+    _i32(lens)
+    _lib.lib().od_uhead_tail_bwd_varlen(_p(fsum), _p(mod), _p(w_out), _p(b_out), _p(du), _p(dfm), _p(dmod), _p(dw_out),
+                                        _p(db_out), _p(lens), B, U, L, u_scale, _stream(fsum))
+
+
 # ---------------------------------------------------------------- loss / sampler
 def make_xt(x0, x1, t, xt, dsq):
     B, E, L = x0.shape
@@ -457,10 +491,27 @@ def make_xt(x0, x1, t, xt, dsq):
     _lib.lib().od_make_xt(_p(x0), _p(x1), _p(t), _p(xt), _p(dsq), B, E, L, _stream(x0))
 
 
+def make_xt_varlen(x0, x1, t, xt, dsq, lens):
+    """make_xt per sequence (lens: device int32 [B]): dsq[b] over frames < lens[b]; xt = 0 at frames >= lens[b], where x0 / x1 are not read."""
+    B, E, L = x0.shape
+    _f32(x0, x1, t, xt, dsq)
+    _i32(lens)
+    _lib.lib().od_make_xt_varlen(_p(x0), _p(x1), _p(t), _p(xt), _p(dsq), _p(lens), B, E, L, _stream(x0))
+
+
 def loss_grad(xt, x1, u, v, dsq, dv, sums, c0, osl_w, del_w):
     B, E, L = xt.shape
     _f32(xt, x1, u, v, dsq, dv, sums)
     _lib.lib().od_loss_grad(_p(xt), _p(x1), _p(u), _p(v), _p(dsq), _p(dv), _p(sums), B, E, L, c0, osl_w, del_w, _stream(xt))
+
+
+def loss_grad_varlen(xt, x1, u, v, dsq, dv, sums, lens, c0, osl_w, del_w):
+    """loss_grad per sequence: sums over frames < lens[b], normalised by lens[b]; dv = 0 at frames >= lens[b]."""
+    B, E, L = xt.shape
+    _f32(xt, x1, u, v, dsq, dv, sums)
+    _i32(lens)
+    _lib.lib().od_loss_grad_varlen(_p(xt), _p(x1), _p(u), _p(v), _p(dsq), _p(dv), _p(sums), _p(lens), B, E, L, c0, osl_w, del_w,
+                                   _stream(xt))
 
 
 def loss_finalize(sums, dsq, u, out, du, c0, osl_w, del_w):

@@ -16,7 +16,7 @@ from torch import nn
 
 from . import ops
 from .lr_schedule import LRScheduleArgs, make_lr_schedule
-from .model import DiffusionModel, DiffusionModelArgs, _coerce_args
+from .model import DiffusionModel, DiffusionModelArgs, _coerce_args, valid_frames, zero_padding
 from .optim import FusedAdamWEMA
 
 try:  # optional: the GPU image does not ship Lightning
@@ -101,9 +101,13 @@ class DiffusionTrainer(_Base):
         self._logged: Dict[str, torch.Tensor] = {}
 
     # ------------------------------------------------------------------ loss (train.py:69-108)
-    def forward(self, model: DiffusionModel, h, x1, s, _labels=None, *, t=None, x0=None):
+    def forward(self, model: DiffusionModel, h, x1, s, labels=None, *, lengths=None, t=None, x0=None):
         """Distance-marching loss.  `t` / `x0` may be passed to pin the noise (parity tests);
-        by default they are drawn as the reference does: stratified logit-normal t, x0 ~ N(0,I)."""
+        by default they are drawn as the reference does: stratified logit-normal t, x0 ~ N(0,I).
+        `lengths` (B ints): the ragged step — row b is a sequence of lengths[b] frames padded to L.  Every frame mean, the u-head's mean,
+        attention and the convs' zero padding keep to a sequence's own frames, and loss / osl / del / u_mape are the means over the B
+        sequences: the loss is (1/B) * sum_b of what this call returns on sequence b alone at L = lengths[b] with the same t[b], x0[b], and
+        every parameter gradient is the mean of those calls' gradients.  The padding of h, x1 and x0 is never read: it may hold anything."""
         B = x1.size(0)
         dev = x1.device
         if t is None:
@@ -112,7 +116,8 @@ class DiffusionTrainer(_Base):
         if x0 is None:
             x0 = torch.randn_like(x1, dtype=torch.float32)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())
-        out = _TrainLossFn.apply(model, self.osl_weight, self.del_weight, needs_grad, h, x1, s, t, x0,
+        lens = None if lengths is None else [int(n) for n in torch.as_tensor(lengths).tolist()]
+        out = _TrainLossFn.apply(model, self.osl_weight, self.del_weight, needs_grad, lens, h, x1, s, t, x0,
                                  *(model.parameters() if needs_grad else ()))
         loss = out[0]
         logs = {"loss": out[0].detach(), "osl": out[1].detach(), "del": out[2].detach(), "u_mape": out[3].detach()}
@@ -136,7 +141,11 @@ class DiffusionTrainer(_Base):
             self.log_dict(d)
 
     def training_step(self, batch, batch_idx):
-        loss, log_dict = self(self.diffusion, *batch)
+        if len(batch) == 5:                                  # data.RaggedLatentBatch(h, z, s, labels, lengths)
+            h, z, s, labels, lengths = batch
+            loss, log_dict = self(self.diffusion, h, z, s, labels, lengths=lengths)
+        else:
+            loss, log_dict = self(self.diffusion, *batch)
         self._log({f"train/{k}": v for k, v in log_dict.items()})
         return loss
 
@@ -165,7 +174,7 @@ class _TrainLossFn(torch.autograd.Function):
     (all HIP kernels).  backward: the denoiser backward, scaled by the incoming grad."""
 
     @staticmethod
-    def forward(ctx, model: DiffusionModel, osl_w, del_w, needs_grad, h, x1, s, t, x0, *params):
+    def forward(ctx, model: DiffusionModel, osl_w, del_w, needs_grad, lens, h, x1, s, t, x0, *params):
         f = model._f32c
         h, x1, s, t, x0 = f(h), f(x1), f(s), f(t), f(x0)
         B, E, L = x1.shape
@@ -174,7 +183,7 @@ class _TrainLossFn(torch.autograd.Function):
             h = h.expand(B, -1, -1).contiguous()
         eng, dt = model.engine, model._dtype()
         eng.pack_weights(dt, train=needs_grad)
-        eng.plan(B, L, h.shape[0], dt, train=needs_grad)
+        eng.plan(B, L, h.shape[0], dt, train=needs_grad, lens=lens)
         xt = eng.buf("loss.xt", (B, E, L), torch.float32)
         dsq = eng.buf("loss.dsq", (B,), torch.float32)
         sums = eng.buf("loss.sums", (B, 3), torch.float32)
@@ -184,12 +193,22 @@ class _TrainLossFn(torch.autograd.Function):
         du = eng.buf("loss.du", (B,), torch.float32)
         dsq.zero_()
         sums.zero_()
-        ops.make_xt(x0, x1, t, xt, dsq)
+        if lens is not None:
+            # ragged: the audio's padding is read by real GEMMs and must be finite — it is zero-filled here, whatever the batch holds there;
+            # x0's and x1's padding is never read (od_make_xt_varlen / od_loss_grad_varlen select by frame)
+            h = zero_padding(h, valid_frames(lens, L, dev))
+            lens_d = eng.ws.t["vl.lens"]
+            ops.make_xt_varlen(x0, x1, t, xt, dsq, lens_d)
+        else:
+            ops.make_xt(x0, x1, t, xt, dsq)
         eng.conditioning(h, s)
         eng.pred(xt, u, v)
         out = torch.empty(4, dtype=torch.float32, device=dev)
         eng._det_flush(dsq)                              # (OD_DETERMINISTIC: make_xt's per-sample sums, read by loss_grad)
-        ops.loss_grad(xt, x1, u, v, dsq, dv, sums, model.c0, osl_w, del_w)
+        if lens is not None:
+            ops.loss_grad_varlen(xt, x1, u, v, dsq, dv, sums, lens_d, model.c0, osl_w, del_w)
+        else:
+            ops.loss_grad(xt, x1, u, v, dsq, dv, sums, model.c0, osl_w, del_w)
         eng._det_flush(sums)
         ops.loss_finalize(sums, dsq, u, out, du, model.c0, osl_w, del_w)
         ctx.model, ctx.style, ctx.nparams = model, s, len(params)
@@ -206,4 +225,4 @@ class _TrainLossFn(torch.autograd.Function):
             du.mul_(g_loss)
             dv.mul_(g_loss)
         eng.backward(t["loss.xt"], ctx.style, du, dv, reducer=getattr(model, "_reducer", None))
-        return (None,) * 9 + (None,) * ctx.nparams
+        return (None,) * 10 + (None,) * ctx.nparams
