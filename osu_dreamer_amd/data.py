@@ -62,7 +62,8 @@ class LatentBatch(NamedTuple):
 
 class RaggedLatentBatch(NamedTuple):
     """N whole maps of different lengths, zero-padded to a common Lpad: map b is valid for frames < lengths[b].  What
-    `LatentDataModule(seq_len=None, batch_size=N > 1)` collates and `DiffusionTrainer.training_step` accepts beside the 4-tuple."""
+    `LatentDataModule(seq_len=None, batch_size=N > 1)` collates (and, with `batch_frames`, what its bucketed loader yields, N = 1 included)
+    and `DiffusionTrainer.training_step` accepts beside the 4-tuple."""
     h: torch.Tensor        # (N, A, Lpad)
     z: torch.Tensor        # (N, E, Lpad)
     s: torch.Tensor        # (N, S)
@@ -81,6 +82,56 @@ def collate_ragged(samples: List[LatentBatch], pad_multiple: int = 64) -> Ragged
         h[i, :, :n], z[i, :, :n] = b.h[..., :n], b.z
     return RaggedLatentBatch(h, z, torch.stack([b.s for b in samples]), torch.stack([b.labels for b in samples]),
                              torch.tensor(lens, dtype=torch.int64))
+
+
+def _roundup(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+def cut_batches(lengths: List[int], batch_frames: int, batch_size: int, pad_multiple: int = 64) -> List[List[int]]:
+    """Indices of `lengths` grouped into frame-budget batches: sorted by length (longest first, ties in arrival order) and cut greedily — a
+    batch opened by a map of n frames has Lpad = roundup(n, pad_multiple) and takes the next-shorter maps while (count + 1) * Lpad <=
+    batch_frames and count < batch_size.  Every index appears once; a map whose Lpad alone exceeds the budget still gets a batch of its own
+    (LatentDataModule refuses the configuration that could produce one)."""
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])          # sorted() is stable: ties keep arrival order
+    out: List[List[int]] = []
+    i = 0
+    while i < len(order):
+        Lpad = _roundup(lengths[order[i]], pad_multiple)
+        n = 1
+        while i + n < len(order) and n < batch_size and (n + 1) * Lpad <= batch_frames:
+            n += 1
+        out.append(order[i:i + n])
+        i += n
+    return out
+
+
+class BucketedBatches(IterableDataset):
+    """Length-bucketed, frame-budget batches over a whole-map LatentDataset, per loader worker: gather `bucket_pool` samples of the dataset's
+    stream (after its shard, shuffle buffer and max_len window), cut them with `cut_batches`, shuffle the pool's batches with the worker's
+    RNG (the `random` module, seeded by LatentDataset.__iter__: a run is reproducible from its seed) and yield each as a RaggedLatentBatch.
+    The partial pool at the end of the stream is cut the same way: no map is dropped."""
+
+    def __init__(self, dataset: "LatentDataset", batch_frames: int, batch_size: int, bucket_pool: int, pad_multiple: int = 64):
+        super().__init__()
+        self.dataset, self.batch_frames, self.batch_size = dataset, batch_frames, batch_size
+        self.bucket_pool, self.pad_multiple = bucket_pool, pad_multiple
+
+    def _cut(self, pool: List[LatentBatch]) -> Iterator[RaggedLatentBatch]:
+        groups = cut_batches([int(b.z.size(-1)) for b in pool], self.batch_frames, self.batch_size, self.pad_multiple)
+        random.shuffle(groups)
+        for g in groups:
+            yield collate_ragged([pool[i] for i in g], self.pad_multiple)
+
+    def __iter__(self):
+        pool: List[LatentBatch] = []
+        for sample in self.dataset:
+            pool.append(sample)
+            if len(pool) == self.bucket_pool:
+                yield from self._cut(pool)
+                pool = []
+        if pool:
+            yield from self._cut(pool)
 
 
 def load_latents(latent_file: Path) -> LatentBatch:
@@ -192,23 +243,51 @@ class LatentDataModule:
     """Same constructor keys as the reference's LatentDataModule (they are the YAML `data:` block), plus `max_len` and `pad_multiple` for
     ragged training: with `seq_len: null` and `batch_size` N > 1 the training loader collates N whole maps into one `RaggedLatentBatch`,
     zero-padded to the longest map rounded up to `pad_multiple`; a map longer than `max_len` contributes a random window of `max_len`
-    frames, which bounds the step's memory.  With an integer `seq_len` nothing changes."""
+    frames, which bounds the step's memory.  With an integer `seq_len` nothing changes.
+
+    `batch_frames` F (with `seq_len: null` and `max_len` only) sizes a batch by its padded frames instead of its songs: every batch holds
+    B * Lpad <= F, `batch_size` becomes the cap on B, and maps of similar length share a batch (BucketedBatches: each worker sorts a pool of
+    `bucket_pool` maps by length and cuts it from the longest).  No map is dropped.  `bucket_pool` defaults to 64 x `batch_size`: a pool holds
+    whole maps on the host, per worker (0.8 MB for 1500 latent frames at the default widths, so 0.4 GB at batch_size 8), and the padding
+    left in a batch falls with the number of maps that are sorted together, so the default gathers 64 full batches' worth before it cuts.
+    Without `batch_frames` the loaders are what they were."""
 
     def __init__(self, batch_size: int, seq_len: Optional[int], num_workers: int, max_val_count: int = 512,
                  max_val_frac: float = .3, data_path: str = "./data", shuffle_buffer_size: int = 1,
-                 max_per_map: int = -1, rank: int = 0, world_size: int = 1, max_len: Optional[int] = None, pad_multiple: int = 64):
+                 max_per_map: int = -1, rank: int = 0, world_size: int = 1, max_len: Optional[int] = None, pad_multiple: int = 64,
+                 batch_frames: Optional[int] = None, bucket_pool: Optional[int] = None):
         self.batch_size, self.seq_len, self.num_workers = batch_size, seq_len, num_workers
         if seq_len is not None and max_len is not None:
             raise ValueError("data.max_len bounds whole maps: it applies with seq_len: null only")
         if max_len is not None and max_len < 1 or pad_multiple < 1:
             raise ValueError(f"invalid {max_len=} / {pad_multiple=}")
         self.max_len, self.pad_multiple = max_len, int(pad_multiple)
-        self.ragged = seq_len is None and batch_size > 1
+        if batch_frames is None and bucket_pool is not None:
+            raise ValueError("data.bucket_pool is the pool of the frame-budget loader: set data.batch_frames, or drop data.bucket_pool")
+        if batch_frames is not None:
+            if seq_len is not None:
+                raise ValueError("data.batch_frames sizes batches of whole maps: set data.seq_len: null, or drop data.batch_frames")
+            if max_len is None:
+                raise ValueError("data.batch_frames needs data.max_len: without it one long map could exceed the frame budget")
+            if batch_size < 1:
+                raise ValueError(f"data.batch_size is the cap on songs per batch under data.batch_frames: it must be >= 1, got {batch_size}")
+            if _roundup(int(max_len), self.pad_multiple) > int(batch_frames):
+                raise ValueError(f"data.max_len={max_len} rounded up to data.pad_multiple={pad_multiple} is {_roundup(int(max_len), self.pad_multiple)} "
+                                 f"frames, more than data.batch_frames={batch_frames}: raise data.batch_frames or lower data.max_len")
+            bucket_pool = 64 * batch_size if bucket_pool is None else int(bucket_pool)
+            if bucket_pool < 1:
+                raise ValueError(f"data.bucket_pool must be >= 1, got {bucket_pool}")
+        self.batch_frames = None if batch_frames is None else int(batch_frames)
+        self.bucket_pool = bucket_pool
+        self.ragged = seq_len is None and (batch_size > 1 or batch_frames is not None)
         train, val = hold_out_mapsets(Path(data_path), "*.latent.npz", max_val_count, max_val_frac)
         self.train_set = LatentDataset(train, seq_len, shuffle_buffer_size, max_per_map, rank, world_size, max_len=max_len)
         self.val_set = LatentDataset(val)
 
     def train_dataloader(self):
+        if self.batch_frames is not None:             # the dataset yields ready RaggedLatentBatches
+            return DataLoader(BucketedBatches(self.train_set, self.batch_frames, self.batch_size, self.bucket_pool, self.pad_multiple),
+                              batch_size=None, num_workers=self.num_workers, pin_memory=True, persistent_workers=self.num_workers > 0)
         collate = {"collate_fn": self._collate} if self.ragged else {}
         return DataLoader(self.train_set, batch_size=self.batch_size, num_workers=self.num_workers, pin_memory=True,
                           persistent_workers=self.num_workers > 0, drop_last=True, **collate)

@@ -17,6 +17,7 @@ same buckets go through `torch.distributed.all_reduce` on the gloo group instead
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import List, Optional
@@ -88,6 +89,7 @@ class GradBucketReducer:
         self._comm_stream: Optional[torch.cuda.Stream] = None
         self.bucket_log: list = []
         self._done = set()
+        self._deferred = False              # inside no_sync(): a micro-batch of an accumulation group that is not its last
         # exposed communication: HIP events on the compute stream either side of its wait for the side stream, i.e. how long the
         # optimizer had to wait for the exchange after the backward's own kernels were done (0 when the overlap is perfect)
         self.time_exposed = False
@@ -131,9 +133,21 @@ class GradBucketReducer:
             return None
         return dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """Gradient accumulation: a backward inside this context adds into the arena's gradient and exchanges nothing.  Every bucket goes out
+        once per optimizer step, in the usual completion order, during the group's last backward (run outside the context) — holding then
+        the sum over the group's micro-batches.  Under OD_DETERMINISTIC each backward has folded its integer shadows into the arena segment
+        by segment (DenoiserEngine._det_flush_segment) before it reports the segment, deferred or not, so the exchange sees folded values."""
+        self._deferred = True
+        try:
+            yield
+        finally:
+            self._deferred = False
+
     def segment_done(self, name: str):
         """Called by DenoiserEngine.backward when all kernels writing `name`'s gradients are enqueued."""
-        if name in self._done:
+        if self._deferred or name in self._done:
             return
         self._done.add(name)
         s, e = self.segments[name]

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import OrderedDict
 from typing import Dict, List, Optional
 
 import torch
@@ -28,6 +29,14 @@ from ._lib import OD_ACT_NONE, OD_ACT_SILU
 OD_FUSE_FILM_DWCONV_DEFAULT = "0"       # (see DenoiserEngine.pred)
 
 FP32_EPS = float(torch.finfo(torch.float32).eps)   # nn.RMSNorm(eps=None), common/attn.py:71-72
+
+# Training plans kept alive beside the current one (DenoiserEngine.plan), least recently used first out.  OD_PLAN_CACHE overrides; 1 = only the
+# current plan, which is what the engine did before frame-budget batches.  A switch to a key that is not cached costs 0.7 ms at the default model
+# (a step is 15 ms) and an epoch of frame-budget batches of 300 .. 1500-frame maps plans 15 keys: profiles/r13_bucketed_train.txt.  Under OD_DETERMINISTIC at most 2 are kept: every plan registers six
+# accumulation buffers with their 64-bit shadows, and the device table of registered ranges (od_common.h OdDetTable: 20 entries, walked by
+# every accumulating kernel) is sized for the gradient arena and two live plans.
+PLAN_CACHE_DEFAULT = 16
+PLAN_CACHE_DETERMINISTIC = 2
 
 
 def _ceil(x: int, m: int) -> int:
@@ -80,6 +89,11 @@ class DenoiserEngine:
         self._packed_key = None
         self._plan_key = None
         self.ws: Optional[Workspace] = None
+        # training workspaces by plan key, most recently used last: a frame-budget run alternates between a handful of (B, Lpad) and returns
+        # to a workspace it already has instead of allocating, zero-filling and re-deriving the RoPE table (see plan)
+        self._plans: "OrderedDict[tuple, Workspace]" = OrderedDict()
+        self.plan_switches = 0              # how often plan() changed the key / how many of those allocated a new workspace
+        self.plan_builds = 0
         self._rowmap = None
         # bumped whenever the workspace or the packed weights are re-allocated: anything that captured their addresses
         # (the sampler's hipGraph) is stale from then on
@@ -187,11 +201,28 @@ class DenoiserEngine:
         ngroups = len(offs) - 1 if offs is not None else 0
         key = (B, L, Ba, dtype, train, dev, x3, getattr(self.model, "attn_dtype", None), varlen, ngroups)
         if key != self._plan_key:
-            self.ws = Workspace(dev)
+            # A training plan's workspace stays alive in a bounded LRU cache, so a run whose (B, Lpad) changes from step to step returns to
+            # the buffers of an earlier key.  A workspace belongs to ONE key: nothing another plan wrote is ever seen through it, it holds what
+            # that key's own last step left (as two steps in a row on one key always did), and its OD_DETERMINISTIC shadows stay registered
+            # for as long as it lives.  Memory: at most `limit` workspaces, each that of one step at its own B * L rows.  No-grad plans
+            # (validation re-plans per map length, the samplers) are not kept: they would push the training plans out.
+            self.plan_switches += 1
+            self.ws = self._plans.get(key) if train else None
+            if self.ws is None:
+                self.plan_builds += 1
+                self.ws = Workspace(dev)
+                tab = self.ws.get("rope", (L, self.hd // 2, 2), torch.float32)
+                ops.rope_table(tab, L, self.hd)
+            if train:
+                limit = max(1, int(os.environ.get("OD_PLAN_CACHE", PLAN_CACHE_DEFAULT)))
+                if det.enabled():
+                    limit = min(limit, PLAN_CACHE_DETERMINISTIC)
+                self._plans[key] = self.ws
+                self._plans.move_to_end(key)
+                while len(self._plans) > limit:
+                    self._plans.popitem(last=False)
             self._plan_key = key
             self.generation += 1
-            tab = self.ws.get("rope", (L, self.hd // 2, 2), torch.float32)
-            ops.rope_table(tab, L, self.hd)
         self.varlen = varlen
         if varlen:
             lens_t = torch.as_tensor(lens).to("cpu", torch.int32)

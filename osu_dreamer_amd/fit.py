@@ -9,7 +9,8 @@ that config uses, calling the same hooks in the same order:
   the optimizer pass) · AdamW + LambdaLR stepped per batch · on_train_batch_end (EMA) ·
   validation over full maps with the EMA weights · ModelCheckpoint(monitor=val/loss, mode=min,
   save_top_k=1) · resume from --ckpt-path · log_every_n_steps · devices N (one process per GPU,
-  gradient exchange by osu_dreamer_amd.ddp.GradBucketReducer over RCCL).
+  gradient exchange by osu_dreamer_amd.ddp.GradBucketReducer over RCCL) · accumulate_grad_batches
+  (the denoiser only; Trainer.train_group).
 
 Checkpoints keep Lightning's layout (`state_dict`, `hyper_parameters`, `optimizer_states`,
 `lr_schedulers`, `global_step`, `epoch`) so `export-inference` (models/inference/artifact.py)
@@ -25,6 +26,7 @@ ModelCheckpoint and EarlyStopping on `eval/score` with mode max (`monitor_mode`,
 from __future__ import annotations
 
 import argparse
+import contextlib
 import dataclasses
 import json
 import os
@@ -69,8 +71,12 @@ class Trainer:
                  val_check_interval: Optional[int] = None, limit_val_batches: Optional[int] = None,
                  default_root_dir: str = "runs/denoiser", accelerator: str = "gpu", devices: int = 1,
                  enable_checkpointing: bool = True, monitor: str = "val/loss", monitor_mode: str = "min",
-                 early_stop_patience: Optional[int] = None, early_stop_min_delta: Optional[float] = None, **_ignored):
+                 early_stop_patience: Optional[int] = None, early_stop_min_delta: Optional[float] = None,
+                 accumulate_grad_batches: int = 1, **_ignored):
         self.max_epochs, self.max_steps = max_epochs, max_steps
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"trainer.accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = int(accumulate_grad_batches)   # micro-batches per optimizer step (train_group)
         self.precision = str(precision)
         self.gradient_clip_val = gradient_clip_val
         self.log_every_n_steps = log_every_n_steps
@@ -202,8 +208,48 @@ class Trainer:
             dist.destroy_process_group()
         return out
 
+    def train_group(self, module, opt, sched, batches, device, batch_idx: int = 0):
+        """One optimizer step on `batches` (already on `device`): the group of micro-batches of gradient accumulation, or the one batch of a
+        plain step.  With song counts B_1 .. B_m, micro-batch i's loss is scaled by B_i / sum(B) before backward() — a scale _TrainLossFn
+        applies to du / dv on the device — so the gradient left in the arena is the mean over all sum(B) songs: what one step on the union
+        batch computes (for a ragged group exactly the union's ragged step; for equal counts Lightning's 1 / m).  zero_grad, the clip, the
+        optimizer / scheduler step, the EMA and global_step happen once; a data-parallel reducer exchanges each bucket once, during the last
+        backward.  The logged train/* values are the same weighted means.  One batch: no scale, the launch sequence of a plain step.
+        Returns the step's train/* logs (device scalars)."""
+        m = len(batches)
+        if m < 1:
+            raise ValueError("train_group needs at least one batch")
+        if m > 1 and not hasattr(module, "diffusion"):
+            raise RuntimeError("accumulate_grad_batches > 1 is implemented for the denoiser only: the style and latent models hand out their "
+                               "gradients as views of one step's buffer, which the next micro-batch would overwrite")
+        songs = [int(b[1].size(0)) for b in batches] if m > 1 else [1]
+        reducer = getattr(getattr(module, "diffusion", None), "_reducer", None)
+        means: Dict[str, Any] = {}
+        opt.zero_grad()
+        for i, batch in enumerate(batches):
+            quiet = reducer.no_sync() if reducer is not None and i + 1 < m else contextlib.nullcontext()
+            with quiet:
+                with self._autocast(device):
+                    loss = module.training_step(batch, batch_idx + i)
+                if m > 1:
+                    w = songs[i] / sum(songs)
+                    loss = loss * w
+                    for k, v in module._logged.items():
+                        if k.startswith("train/"):
+                            means[k] = v * w + means.get(k, 0.0)
+                loss.backward()
+        if m > 1:
+            module._logged.update(means)
+        opt.step()
+        sched.step()
+        module.on_train_batch_end()
+        self.global_step += 1
+        return {k: v for k, v in getattr(module, "_logged", {}).items() if k.startswith("train/")}
+
     def _fit(self, module, datamodule, ckpt_path, device):
         reducer = None
+        if self.accumulate_grad_batches > 1 and not hasattr(module, "diffusion"):
+            raise RuntimeError(f"trainer.accumulate_grad_batches={self.accumulate_grad_batches} is implemented for fit-denoiser only")
         module.gradient_clip_val = self.gradient_clip_val
         module.to(device)
         if self.precision.startswith("16") and hasattr(module, "diffusion"):
@@ -233,22 +279,22 @@ class Trainer:
         done = False
         while not done:
             it = iter(datamodule.train_dataloader())
-            batch_idx = -1
-            while True:
-                batch = next(it, None)
-                # uneven shards: the epoch ends for every rank as soon as one rank has no batch left
-                if not agree.all_have(batch is not None):
+            batch_idx, dry = 0, False
+            while not dry:
+                # the optimizer step's micro-batches: up to accumulate_grad_batches of them, drawn before any of them runs (their song
+                # counts weight them).  Uneven shards: the ranks agree before every draw, so the group — and with it the epoch — ends for
+                # every rank as soon as one rank has no batch left; the epoch's last, shorter group still makes a step, an empty one none
+                group = []
+                while len(group) < self.accumulate_grad_batches:
+                    batch = next(it, None)
+                    if not agree.all_have(batch is not None):
+                        dry = True
+                        break
+                    group.append(self._to(batch, device))
+                if not group:
                     break
-                batch_idx += 1
-                batch = self._to(batch, device)
-                opt.zero_grad()
-                with self._autocast(device):
-                    loss = module.training_step(batch, batch_idx)
-                loss.backward()
-                opt.step()
-                sched.step()
-                module.on_train_batch_end()
-                self.global_step += 1
+                self.train_group(module, opt, sched, group, device, batch_idx)
+                batch_idx += len(group)
                 if self.global_step % self.log_every_n_steps == 0:
                     opt.check_device_status()          # EVERY rank: a failed launch on one rank must end the job, not train on
                 if self.global_step % self.log_every_n_steps == 0 and self.rank == 0:
@@ -302,9 +348,20 @@ def build_from_config(cfg: Dict[str, Any]):
     m["schedule_args"] = LRScheduleArgs(**m["schedule_args"])
     module = DiffusionTrainer(**m)
     t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "accumulate_grad_batches", "enable_progress_bar", "enable_model_summary", "benchmark"):
+    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
         t.pop(k, None)
+    if t.get("accumulate_grad_batches") is None:
+        t.pop("accumulate_grad_batches", None)
     return module, Trainer(**t)
+
+
+def refuse_accumulation(t: Dict[str, Any], command: str):
+    """`trainer.accumulate_grad_batches` other than 1 for a trainer that cannot accumulate: an error, not a key that is dropped."""
+    k = t.pop("accumulate_grad_batches", None)
+    if k not in (None, 1):
+        raise RuntimeError(f"trainer.accumulate_grad_batches={k} is not implemented for {command}: the model's backward hands out views of a "
+                           "per-step gradient buffer, so a second micro-batch would overwrite the first one's gradients instead of adding to "
+                           "them.  Set trainer.accumulate_grad_batches: 1 (or drop the key); fit-denoiser accumulates")
 
 
 def refuse_ragged_data_parallel(cfg: Dict[str, Any], devices: int):
@@ -343,8 +400,9 @@ def build_style_from_config(cfg: Dict[str, Any]):
     m = dict(cfg["model"])
     m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))       # models/style/model.yml leaves the schedule at its defaults
     t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "accumulate_grad_batches", "enable_progress_bar", "enable_model_summary", "benchmark"):
+    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
         t.pop(k, None)
+    refuse_accumulation(t, "fit-style")
     t.setdefault("monitor", "val/energy_dist")
     t.setdefault("default_root_dir", "runs/style")
     if launch.parse_devices(t.get("devices", 1)) > 1:
@@ -373,8 +431,9 @@ def build_latent_from_config(cfg: Dict[str, Any]):
     m = dict(cfg["model"])
     m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))
     t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "accumulate_grad_batches", "enable_progress_bar", "enable_model_summary", "benchmark"):
+    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
         t.pop(k, None)
+    refuse_accumulation(t, "fit-latent")
     t.setdefault("monitor", "eval/score")
     t.setdefault("monitor_mode", "max")
     t.setdefault("default_root_dir", "runs/latent")
