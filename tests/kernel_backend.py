@@ -41,7 +41,8 @@ BACKENDS = [
 def dev(request):
     """Binds the library for the backend and returns the torch device to allocate on."""
     if request.param == "emu":
-        _lib.use_library(build_emu())
+        if not _built or _lib.loaded_path() != EMU_SO:       # bound already: binding parses the header again, ~10 ms a test
+            _lib.use_library(build_emu())
         return torch.device("cpu")
     if not torch.cuda.is_available():
         pytest.skip("hip backend selected but no GPU is visible")
