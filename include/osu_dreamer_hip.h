@@ -101,6 +101,18 @@ int od_linear_small_bwd(const float* x, const float* W, const float* pre, const 
 /* (B,C,L) fp32 channel-major -> [B*L][C] frame-major of dtype.  replaces the implicit
  * layout of audio at model.py:120. */
 int od_cl_to_frames(int dtype, const float* src, void* dst, int ldd, int B, int C, int L, void* stream);
+/* One padded, channel-major fp32 batch out[N][C][Lpad] gathered from a flat fp32 device store of store_elems elements (the resident feed,
+ * osu_dreamer_amd/resident.py).  Per output row n, read on the device: base[n] (int64) = element offset of channel 0 at the first wanted
+ * frame (a window's start is folded in), cstride[n] (int64) = distance between channels = the frame count of the map or mapset the row comes
+ * from, lens[n] (int32) = valid frames, 1 <= lens[n] <= Lpad.
+ *   out[n][c][l] = l < lens[n] ? store[base[n] + c * cstride[n] + l] : 0
+ * The zeros are selected, not multiplied (out may hold anything on entry), and nothing at or past lens[n] of a row is loaded, so a row may
+ * end the store.  base[n] is arbitrary: rows whose source and destination are both 16-byte aligned move 16 bytes per lane, the others a
+ * dword.  A row whose descriptor does not lie inside the store comes back as NaN.  OD_ERR_ARG: a null pointer or N, C, Lpad, store_elems < 1.
+ * replaces: data/modules/latent.py:74-80 with the window slices of LatentDataset.make_samples, and collate_ragged here — the
+ * host loader's load, crop, zero-padded collate and host-to-device copy of a batch. */
+int od_feed_gather(const float* store, long store_elems, const long* base, const long* cstride, const int* lens, float* out,
+                   int N, int C, int Lpad, void* stream);
 /* x[m][c] = sum_e W[c][e] xt[b][e][l] + bias[c].  replaces: model.py:95 (proj_in). */
 int od_proj_in(int dtype, const float* xt, const float* W, const float* bias, void* x, int ldx, int B, int E, int L,
                int D, void* stream);

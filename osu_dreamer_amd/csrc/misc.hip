@@ -22,6 +22,56 @@ __global__ __launch_bounds__(256) void cl_to_frames_kernel(const float* __restri
     }
 }
 
+// ------------------------------------------------------------ resident feed: flat fp32 store -> padded (N, C, Lpad) batch
+// A wave owns FG_SEG frames of one (n, c) row, so the row's descriptor (base, channel stride, valid length) and the choice of path are
+// wave-uniform.  A pure copy, bound by bandwidth: 16 bytes per lane when the row's source and destination are both 16-byte aligned
+// (1 KiB per wave-instruction), else one dword per lane with four independent loads in flight (256 contiguous bytes per wave-instruction
+// on both sides: the shape that still streams at the memory's rate; the destination alone being aligned does not help, a 16-byte store fed
+// by four strided dword loads touches every line four times).  Frames >= len are SELECTED as zero, never loaded: the quad that straddles
+// len is peeled element by element, so a row that ends the store is not read past.  A row whose descriptor does not lie inside the store
+// (or whose len is outside 1..Lpad) is written as NaN and nothing of it is loaded.
+constexpr int FG_SEG = 1024;
+__global__ __launch_bounds__(256) void feed_gather_kernel(const float* __restrict__ store, long store_elems, const long* __restrict__ base,
+                                                          const long* __restrict__ cstride, const int* __restrict__ lens,
+                                                          float* __restrict__ out, int C, int Lpad, int nseg, long items) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
+    if (w >= items) return;
+    const long row = w / nseg;
+    const int seg = (int)(w - row * nseg);
+    const int n = (int)(row / C), c = (int)(row - (long)n * C);
+    const long b0 = base[n], cs = cstride[n];
+    int len = lens[n];
+    const long s0 = b0 + (long)c * cs;                      // 64-bit: a real store exceeds 2^31 elements
+    const bool ok = len >= 1 && len <= Lpad && b0 >= 0 && cs >= 0 && s0 >= 0 && s0 <= store_elems - len;
+    const float fill = ok ? 0.f : __builtin_nanf("");
+    if (!ok) len = 0;
+    const float* src = store + s0;                          // dereferenced under l < len only
+    float* dst = out + row * Lpad;
+    const int l0 = seg * FG_SEG;
+    const int l1 = l0 + FG_SEG < Lpad ? l0 + FG_SEG : Lpad;
+    if ((Lpad & 3) == 0 && ((((size_t)src) | ((size_t)dst)) & 15) == 0) {
+        for (int l = l0 + lane * 4; l < l1; l += 256) {     // Lpad % 4 == 0: a quad that starts below l1 ends at or below it
+            f32x4 v;
+            if (l + 4 <= len) v = *(const f32x4*)(src + l);
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) v[e] = l + e < len ? src[l + e] : fill;
+            }
+            *(f32x4*)(dst + l) = v;
+        }
+    } else {
+        for (int l = l0 + lane; l < l1; l += 256) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[e] = l + 64 * e < len ? src[l + 64 * e] : fill;
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (l + 64 * e < l1) dst[l + 64 * e] = v[e];
+        }
+    }
+}
+
 // ------------------------------------------------------------ proj_in: E (<=8) channels -> D
 template <class T>
 __global__ __launch_bounds__(256) void proj_in_kernel(const float* __restrict__ xt, const float* __restrict__ W,
@@ -483,6 +533,17 @@ __global__ __launch_bounds__(256) void pack_weight_split_kernel(const float* __r
 extern "C" int od_cl_to_frames(int dtype, const float* src, void* dst, int ldd, int B, int C, int L, void* stream) {
     dim3 grid((L + 63) / 64, (C + 63) / 64, B);
     DISPATCH_T(dtype, OD_LAUNCH((cl_to_frames_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, src, (T_*)dst, ldd, C, L));
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_feed_gather(const float* store, long store_elems, const long* base, const long* cstride, const int* lens, float* out,
+                              int N, int C, int Lpad, void* stream) {
+    if (!store || !base || !cstride || !lens || !out || Lpad < 1 || N < 1 || C < 1 || store_elems < 1) return OD_ERR_ARG;
+    const int nseg = (Lpad + FG_SEG - 1) / FG_SEG;
+    const long items = (long)N * C * nseg, blocks = (items + 3) / 4;
+    if (blocks > 0x7fffffffL) return OD_ERR_UNSUPPORTED;
+    OD_LAUNCH(feed_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, store, store_elems, base, cstride, lens, out, C, Lpad, nseg, items);
     OD_CHECK_LAUNCH();
     return 0;
 }

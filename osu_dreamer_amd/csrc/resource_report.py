@@ -1,7 +1,7 @@
 """Summarise hipcc -Rpass-analysis=kernel-resource-usage output (VGPR / scratch / LDS per kernel)."""
 import re, subprocess, sys
 txt = open(sys.argv[1]).read()
-blocks = re.split(r'remark: Function Name: ', txt)[1:]
+blocks = re.split(r'remark: (?:\S+: )?Function Name: ', txt)[1:]      # newer hipcc puts file:line:col in front of every remark
 flt = sys.argv[2] if len(sys.argv) > 2 else ''
 for b in blocks:
     name = b.split(' ')[0]

@@ -373,6 +373,26 @@ def refuse_ragged_data_parallel(cfg: Dict[str, Any], devices: int):
                            "data.seq_len) on several devices")
 
 
+def build_latent_data(data: Dict[str, Any], trainer: "Trainer", style_only: bool = False, **shard):
+    """The `data:` block -> its data module.  `data.resident: true` keeps the training set on the device (resident.py: every file read once,
+    batches gathered by od_feed_gather), within `data.resident_max_gb` when that is set; fit-style's store holds the style fields only."""
+    resident, max_gb = data.pop("resident", False), data.pop("resident_max_gb", None)
+    if not resident:
+        if max_gb is not None:
+            raise ValueError("data.resident_max_gb bounds the resident store: set data.resident: true, or drop the key")
+        return LatentDataModule(**data, **shard)
+    from .resident import STYLE_FIELDS, ALL_FIELDS, ResidentLatentDataModule
+    if data.get("num_workers") and trainer.rank == 0:
+        print(f"data.resident: batches are gathered on the device, data.num_workers={data['num_workers']} is ignored for training")
+    if torch.cuda.is_available():
+        device = torch.device("cuda", trainer.local_rank)
+    elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
+        device = torch.device("cpu")         # test-suite only, as in Trainer.fit
+    else:
+        raise RuntimeError("data.resident needs an MI355X: the store lives in device memory")
+    return ResidentLatentDataModule(**data, **shard, device=device, fields=STYLE_FIELDS if style_only else ALL_FIELDS, resident_max_gb=max_gb)
+
+
 def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
     """begin a training run for the diffusion model (reference: scripts/fit_denoiser.py:17-32)."""
     with open(config) as f:
@@ -390,7 +410,7 @@ def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, 
         raise RuntimeError(f"fit_denoiser() with trainer.devices={devices} must run inside a rank: use `python -m osu_dreamer_amd "
                            f"fit-denoiser` (it starts the {devices} ranks) or `torchrun --nproc-per-node {devices}`")
     module, trainer = build_from_config(cfg)
-    data = LatentDataModule(**cfg["data"], rank=trainer.rank, world_size=trainer.world)
+    data = build_latent_data(dict(cfg["data"]), trainer, rank=trainer.rank, world_size=trainer.world)
     trainer.fit(module, data, ckpt_path=ckpt_path)
     return module, trainer
 
@@ -421,7 +441,7 @@ def fit_style(config: str = DEFAULT_STYLE_CONFIG, ckpt_path: Optional[str] = Non
     if cfg.get("seed_everything") not in (None, False):
         seed_everything(cfg["seed_everything"])
     module, trainer = build_style_from_config(cfg)
-    data = LatentDataModule(**cfg["data"])
+    data = build_latent_data(dict(cfg["data"]), trainer, style_only=True)
     trainer.fit(module, data, ckpt_path=ckpt_path)
     return module, trainer
 

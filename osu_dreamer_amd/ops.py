@@ -169,6 +169,18 @@ def cl_to_frames(src, dst):
     _lib.lib().od_cl_to_frames(dt_code(dst.dtype), _p(src), _p(dst), _ld(dst), B, C, L, _stream(src))
 
 
+def feed_gather(store, base, cstride, lens, out):
+    """out (N, C, Lpad) fp32 = per row n, lens[n] frames of C channels from the flat fp32 `store` at base[n] + c * cstride[n], zero beyond
+    (base, cstride: device int64 [N]; lens: device int32 [N]).  Every element of out is written."""
+    N, C, Lpad = out.shape
+    _f32(store, out)
+    _lens(lens, N)
+    for t in (base, cstride):
+        assert t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == N and t.is_contiguous(), "base / cstride must be contiguous int64 [N]"
+    assert store.device == out.device == base.device == cstride.device == lens.device, "feed_gather: every tensor on one device"
+    _lib.lib().od_feed_gather(_p(store), store.numel(), _p(base), _p(cstride), _p(lens), _p(out), N, C, Lpad, _stream(out))
+
+
 def proj_in(xt, W, bias, x):
     B, E, L = xt.shape
     D = x.shape[1]

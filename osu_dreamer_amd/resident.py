@@ -1,0 +1,362 @@
+"""Device-resident training data: the encoded dataset lives in HBM and every batch is gathered on the GPU.
+
+`LatentDataModule` (data.py) opens `<map>.latent.npz` and the mapset's `h.npy` for every map, every epoch — `h.npy` once per difficulty of
+the same mapset — collates and zero-pads on the host, pins and copies.  Here every file is read ONCE into a flat fp32 device store
+(`ResidentLatentStore`: `h` once per mapset, `z` per map, `s` / `labels` as tables), an epoch is planned on the host from the maps' lengths
+alone (`EpochPlanner`: integers only), and a batch is built by `od_feed_gather` (csrc/misc.hip) from three small descriptor vectors that go
+up in one stream-ordered copy: no loader workers, no per-epoch file reads, no host collate, no host-to-device copy of the batch.
+
+Memory: a map of L latent frames takes 4 (A L / maps-in-its-mapset + E L + S + 5) bytes — 0.8 MB at L = 1500 and the default widths (A 128,
+E 6) — so tens of thousands of maps fit in an MI355X's 288 GB beside the model; `max_bytes` (YAML: data.resident_max_gb) refuses a store
+that would not, before anything is allocated.
+
+The feed follows the host loader's rules in its three modes (an integer seq_len: fixed windows; seq_len None with batch_size N: N whole
+maps per batch; batch_frames: frame-budget batches cut by data.cut_batches), with one difference that comes with planning a whole epoch at
+once: the order is a full permutation of the epoch's samples instead of a shuffle buffer's, so `shuffle_buffer_size` has no meaning here.
+"""
+from __future__ import annotations
+
+import zipfile
+from pathlib import Path
+from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .data import NUM_LABELS, LatentBatch, LatentDataModule, LatentDataset, RaggedLatentBatch, cut_batches
+
+ALL_FIELDS = ("h", "z", "s", "labels")
+STYLE_FIELDS = ("s", "labels")
+
+
+def _roundup(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+def npz_member_shape(path, member: str) -> Tuple[int, ...]:
+    """Shape of `member` of an .npz, from the member's .npy header (the array is not read)."""
+    with zipfile.ZipFile(path) as z, z.open(member + ".npy") as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        shape, _, _ = read(f)
+    return tuple(int(x) for x in shape)
+
+
+def npy_shape(path) -> Tuple[int, ...]:
+    """Shape of an .npy file, from its header (the array is not read or mapped)."""
+    with open(path, "rb") as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        shape, _, _ = read(f)
+    return tuple(int(x) for x in shape)
+
+
+def shard_files(mapsets: Sequence[Path], rank: int = 0, world_size: int = 1) -> List[Path]:
+    """The rank's share of the dataset: files in `LatentDataset._files()` order, file i to rank i % world_size (the host loader's rank shard)."""
+    return [f for i, f in enumerate(LatentDataset(list(mapsets))._files()) if i % world_size == rank]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ the plan
+class PlanBatch(NamedTuple):
+    """One batch of an epoch plan, host integers only: row i takes frames starts[i] .. starts[i] + lens[i] of map maps[i] (an index into the
+    store's files); Lpad is the batch's padded length (= seq_len for fixed windows)."""
+    maps: np.ndarray       # (B,) int64
+    starts: np.ndarray     # (B,) int64
+    lens: np.ndarray       # (B,) int64
+    Lpad: int
+
+
+class EpochPlanner:
+    """Plans one epoch from the maps' lengths.  The three modes and their rules are LatentDataset.make_samples' and LatentDataModule's:
+
+      * integer `seq_len`: per map, end = L - seq_len + 1 (maps with end < 1 contribute none), start = randint(0, min(seq_len, end)), windows at
+        start, start + seq_len, ... < end, a random subset of at most `max_per_map` of them; all of the epoch's windows are permuted and cut into
+        batches of `batch_size`, the last partial batch dropped (drop_last=True);
+      * `seq_len` None, `batch_size` N: a permutation of the maps in chunks of N, a map longer than `max_len` contributing a random window of
+        max_len frames, Lpad = the chunk's longest rounded up to `pad_multiple`; the last partial chunk is dropped;
+      * `batch_frames`: pools of `bucket_pool` consecutive maps of the permutation go through data.cut_batches, each pool's batches are
+        shuffled, and the partial last pool is cut too: no map is dropped.
+    """
+
+    def __init__(self, lengths: Sequence[int], batch_size: int, seq_len: Optional[int], max_per_map: int = -1, max_len: Optional[int] = None,
+                 pad_multiple: int = 64, batch_frames: Optional[int] = None, bucket_pool: Optional[int] = None):
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self.batch_size, self.seq_len = int(batch_size), seq_len
+        self.max_per_map = int(max_per_map) if max_per_map > 0 else None
+        self.max_len, self.pad_multiple = max_len, int(pad_multiple)
+        self.batch_frames = batch_frames
+        self.bucket_pool = (64 * self.batch_size if bucket_pool is None else int(bucket_pool)) if batch_frames is not None else None
+
+    def plan(self, gen: torch.Generator) -> List[PlanBatch]:
+        if self.seq_len is not None:
+            return self._windows(gen)
+        return self._bucketed(gen) if self.batch_frames is not None else self._chunks(gen)
+
+    # ---- fixed windows
+    def _windows(self, gen) -> List[PlanBatch]:
+        T = int(self.seq_len)
+        end = self.lengths - T + 1
+        live = np.nonzero(end >= 1)[0]
+        if len(live) == 0:
+            return []
+        end = end[live]
+        hi = np.minimum(T, end)
+        start = np.minimum((torch.rand(len(live), generator=gen, dtype=torch.float64).numpy() * hi).astype(np.int64), hi - 1)
+        count = (end - start + T - 1) // T                      # len(arange(start, end, T)) >= 1
+        maps, starts = [], []
+        if self.max_per_map == 1:                               # the shipped configs: one random window per map, no per-map loop
+            pick = np.minimum((torch.rand(len(live), generator=gen, dtype=torch.float64).numpy() * count).astype(np.int64), count - 1)
+            maps, starts = [live], [start + pick * T]
+        else:
+            for m, s0, k in zip(live.tolist(), start.tolist(), count.tolist()):
+                idx = np.arange(k, dtype=np.int64)
+                if self.max_per_map is not None and k > self.max_per_map:
+                    idx = torch.randperm(k, generator=gen)[:self.max_per_map].numpy()
+                maps.append(np.full(len(idx), m, dtype=np.int64))
+                starts.append(s0 + idx * T)
+        maps, starts = np.concatenate(maps), np.concatenate(starts)
+        perm = torch.randperm(len(maps), generator=gen).numpy()
+        maps, starts = maps[perm], starts[perm]
+        B = self.batch_size
+        lens = np.full(B, T, dtype=np.int64)
+        return [PlanBatch(maps[i:i + B], starts[i:i + B], lens, T) for i in range(0, len(maps) - B + 1, B)]
+
+    # ---- whole maps
+    def _whole(self, gen) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """A permutation of the maps with each map's window: (maps, starts, lens)."""
+        maps = torch.randperm(len(self.lengths), generator=gen).numpy()
+        L = self.lengths[maps]
+        starts, lens = np.zeros_like(L), L.copy()
+        if self.max_len is not None:
+            over = L > self.max_len
+            room = np.where(over, L - self.max_len + 1, 1)
+            draw = np.minimum((torch.rand(len(maps), generator=gen, dtype=torch.float64).numpy() * room).astype(np.int64), room - 1)
+            starts, lens = np.where(over, draw, 0), np.where(over, self.max_len, L)
+        return maps, starts, lens
+
+    def _batch(self, maps, starts, lens) -> PlanBatch:
+        return PlanBatch(maps, starts, lens, _roundup(int(lens.max()), self.pad_multiple))
+
+    def _chunks(self, gen) -> List[PlanBatch]:
+        maps, starts, lens = self._whole(gen)
+        N = self.batch_size
+        return [self._batch(maps[i:i + N], starts[i:i + N], lens[i:i + N]) for i in range(0, len(maps) - N + 1, N)]
+
+    def _bucketed(self, gen) -> List[PlanBatch]:
+        maps, starts, lens = self._whole(gen)
+        out: List[PlanBatch] = []
+        for p in range(0, len(maps), self.bucket_pool):
+            sl = slice(p, p + self.bucket_pool)
+            groups = cut_batches(lens[sl].tolist(), self.batch_frames, self.batch_size, self.pad_multiple)
+            for gi in torch.randperm(len(groups), generator=gen).tolist():
+                g = np.asarray(groups[gi], dtype=np.int64) + p
+                out.append(self._batch(maps[g], starts[g], lens[g]))
+        return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- the store
+class ResidentLatentStore:
+    """The rank's share of an encoded dataset on `device`, every file read once.
+
+      data     flat fp32: every mapset's `h` (A, Lh) once, then every map's `z` (E, L), each array as it lies in its file (channel-major);
+               h_base / h_stride / z_base / lengths (host int64, one per map) locate them: channel c of map m's h starts at
+               h_base[m] + c * h_stride[m] (maps of one mapset share the values), of its z at z_base[m] + c * lengths[m]
+      s        (n_maps, S) fp32,  labels (n_maps, 5) fp32: tables for torch.index_select
+      lengths  latent frames per map (z's), on the host: all an epoch plan needs
+
+    `fields` without "h" / "z" (the style model's feed) reads the `s` and `labels` members only and never opens h.npy; the lengths then
+    come from the header of the `z` member (its array is not read).  The upload goes through two pinned staging buffers of `staging_bytes`
+    each, not through a host copy of the dataset.  `max_bytes`: refuse — before anything is allocated — a store that needs more."""
+
+    def __init__(self, mapsets: Sequence[Path], device, fields: Sequence[str] = ALL_FIELDS, rank: int = 0, world_size: int = 1,
+                 max_bytes: Optional[int] = None, staging_bytes: int = 32 << 20):
+        self.device = torch.device(device)
+        self.fields = tuple(fields)
+        if not set(self.fields) <= set(ALL_FIELDS) or not {"s", "labels"} <= set(self.fields) or ("h" in self.fields) != ("z" in self.fields):
+            raise ValueError(f"fields must be {ALL_FIELDS} or {STYLE_FIELDS}, got {self.fields}")
+        self.has_frames = "h" in self.fields
+        self.files = shard_files(mapsets, rank, world_size)
+        if not self.files:
+            raise ValueError(f"no *.latent.npz file for rank {rank} of {world_size}")
+        # ---- sizes from the headers
+        z_shapes = [npz_member_shape(f, "z") for f in self.files]
+        self.lengths = np.asarray([sh[-1] for sh in z_shapes], dtype=np.int64)
+        self.style_dim = int(np.prod(npz_member_shape(self.files[0], "s")))
+        self.emb_dim = int(z_shapes[0][0])
+        n = len(self.files)
+        self.h_base, self.h_stride = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        self.z_base = np.zeros(n, dtype=np.int64)
+        self.a_dim = 0
+        h_files: List[Tuple[Path, int]] = []                   # (mapset's h.npy, its offset), each once
+        elems = 0
+        if self.has_frames:
+            seen = {}
+            for i, f in enumerate(self.files):
+                d = f.parent
+                if d not in seen:
+                    A, Lh = npy_shape(d / "h.npy")
+                    self.a_dim = self.a_dim or A
+                    if A != self.a_dim:
+                        raise ValueError(f"{d / 'h.npy'}: {A} channels, the dataset's other maps have {self.a_dim}")
+                    seen[d] = (elems, Lh)
+                    h_files.append((d / "h.npy", elems))
+                    elems += A * Lh
+                self.h_base[i], self.h_stride[i] = seen[d]
+                if z_shapes[i][0] != self.emb_dim or self.h_stride[i] < self.lengths[i]:
+                    raise ValueError(f"{f}: z {z_shapes[i]} does not fit the dataset (emb_dim {self.emb_dim}) or its mapset's h ({self.h_stride[i]} frames)")
+            for i in range(n):
+                self.z_base[i] = elems
+                elems += self.emb_dim * int(self.lengths[i])
+        self.nbytes = 4 * (elems + n * (self.style_dim + NUM_LABELS))
+        if max_bytes is not None and self.nbytes > max_bytes:
+            raise MemoryError(f"the resident store needs {self.nbytes} bytes ({self.nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than the limit of "
+                              f"{int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or train with data.resident: false")
+        # ---- allocate and fill
+        self.data = torch.empty(max(elems, 1), dtype=torch.float32, device=self.device)
+        s_host, labels_host = np.empty((n, self.style_dim), dtype=np.float32), np.empty((n, NUM_LABELS), dtype=np.float32)
+        up = _Uploader(self.device, staging_bytes)
+        for path, off in h_files:
+            up.put(self.data, off, np.load(path))
+        for i, f in enumerate(self.files):
+            with np.load(f) as d:
+                s_host[i], labels_host[i] = d["s"].reshape(-1), d["labels"].reshape(-1)
+                if self.has_frames:
+                    up.put(self.data, int(self.z_base[i]), d["z"])
+        up.finish()
+        self.s = torch.from_numpy(s_host).to(self.device)
+        self.labels = torch.from_numpy(labels_host).to(self.device)
+
+    def __len__(self):
+        return len(self.files)
+
+
+class _Uploader:
+    """Host arrays -> slices of a flat device tensor through two pinned staging buffers used in turn (a buffer is refilled only after the
+    copy that read it has finished).  On the host (the test-suite's emulator backend) a plain copy."""
+
+    def __init__(self, device, staging_bytes: int):
+        self.cuda = device.type == "cuda"
+        if self.cuda:
+            k = max(1, staging_bytes // 4)
+            self.bufs = [torch.empty(k, dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            self.events = [None, None]
+            self.turn = 0
+            self.stream = torch.cuda.current_stream(device)
+
+    def put(self, dst: torch.Tensor, off: int, arr: np.ndarray):
+        flat = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+        if not self.cuda:
+            dst[off:off + flat.size].copy_(torch.from_numpy(flat))
+            return
+        k = self.bufs[0].numel()
+        for i in range(0, flat.size, k):
+            b = self.turn
+            self.turn ^= 1
+            if self.events[b] is not None:
+                self.events[b].synchronize()
+            m = min(k, flat.size - i)
+            self.bufs[b].numpy()[:m] = flat[i:i + m]
+            dst[off + i:off + i + m].copy_(self.bufs[b][:m], non_blocking=True)
+            self.events[b] = torch.cuda.Event()
+            self.events[b].record(self.stream)
+
+    def finish(self):
+        if self.cuda:
+            self.stream.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ the feed
+class ResidentFeed:
+    """Re-iterable over the batches of one epoch each: every iter() draws a new plan from the feed's generator — seeded, at the first epoch,
+    like LatentDataset.__iter__ (torch.initial_seed() + 7919 * rank) — and yields the plan's batches, built on the device."""
+
+    def __init__(self, store: ResidentLatentStore, planner: EpochPlanner, ragged: bool, rank: int = 0):
+        self.store, self.planner, self.ragged, self.rank = store, planner, ragged, rank
+        self.gen: Optional[torch.Generator] = None
+        self.pin = store.device.type == "cuda"
+
+    def plan_epoch(self) -> List[PlanBatch]:
+        if self.gen is None:
+            self.gen = torch.Generator().manual_seed(torch.initial_seed() + 7919 * self.rank)
+        return self.planner.plan(self.gen)
+
+    def gather(self, pb: PlanBatch):
+        """The device batch of one plan entry: h and z by od_feed_gather, s and labels by index_select.  The descriptors (h base, h channel
+        stride, z base, z channel stride, map index as int64, the lengths as int32 behind them) travel as ONE stream-ordered copy from pinned
+        memory; the pinned block returns to torch's host allocator, which hands it out again only after that copy has run."""
+        st, B = self.store, len(pb.maps)
+        if st.has_frames:
+            # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
+            assert (pb.starts >= 0).all() and (pb.lens >= 1).all() and (pb.lens <= pb.Lpad).all() and (pb.starts + pb.lens <= st.lengths[pb.maps]).all()
+            host = torch.empty(5 * B + (B + 1) // 2, dtype=torch.int64, pin_memory=self.pin)
+            hv = host.numpy()
+            hv[0:B], hv[B:2 * B] = st.h_base[pb.maps] + pb.starts, st.h_stride[pb.maps]
+            hv[2 * B:3 * B], hv[3 * B:4 * B] = st.z_base[pb.maps] + pb.starts, st.lengths[pb.maps]
+            hv[4 * B:5 * B] = pb.maps
+            hv[5 * B:].view(np.int32)[:B] = pb.lens
+            desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
+            desc.copy_(host, non_blocking=True)
+            maps, lens32 = desc[4 * B:5 * B], desc[5 * B:].view(torch.int32)[:B]
+            h = torch.empty(B, st.a_dim, pb.Lpad, dtype=torch.float32, device=st.device)
+            z = torch.empty(B, st.emb_dim, pb.Lpad, dtype=torch.float32, device=st.device)
+            ops.feed_gather(st.data, desc[0:B], desc[B:2 * B], lens32, h)
+            ops.feed_gather(st.data, desc[2 * B:3 * B], desc[3 * B:4 * B], lens32, z)
+        else:
+            host = torch.from_numpy(np.ascontiguousarray(pb.maps))
+            if self.pin:
+                host = host.pin_memory()
+            maps = host.to(st.device, non_blocking=True)
+            h = torch.empty(B, 0, pb.Lpad, dtype=torch.float32, device=st.device)      # the style model reads s and labels only
+            z = torch.empty(B, 0, pb.Lpad, dtype=torch.float32, device=st.device)
+        s, labels = st.s.index_select(0, maps), st.labels.index_select(0, maps)
+        if self.ragged:
+            return RaggedLatentBatch(h, z, s, labels, torch.from_numpy(pb.lens.astype(np.int64)))
+        return LatentBatch(h, z, s, labels)
+
+    def __iter__(self) -> Iterator:
+        for pb in self.plan_epoch():
+            yield self.gather(pb)
+
+
+class ResidentLatentDataModule:
+    """`LatentDataModule` with the training set resident on `device`: the same constructor keys (the YAML `data:` block) and the same three
+    feed modes, plus `device`, `fields` (STYLE_FIELDS for fit-style: s and labels only) and `resident_max_gb`.  `num_workers` serves the
+    denoiser's validation loader only (that one stays the host loader: validation reads whole maps once per check) and
+    `shuffle_buffer_size` nothing: an epoch is a full permutation."""
+
+    def __init__(self, batch_size: int, seq_len: Optional[int], num_workers: int = 0, max_val_count: int = 512, max_val_frac: float = .3,
+                 data_path: str = "./data", shuffle_buffer_size: int = 1, max_per_map: int = -1, rank: int = 0, world_size: int = 1,
+                 max_len: Optional[int] = None, pad_multiple: int = 64, batch_frames: Optional[int] = None, bucket_pool: Optional[int] = None,
+                 device=None, fields: Sequence[str] = ALL_FIELDS, resident_max_gb: Optional[float] = None):
+        # the host module validates the keys, holds out the validation mapsets and keeps the validation loader
+        self.host = LatentDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
+                                     rank, world_size, max_len, pad_multiple, batch_frames, bucket_pool)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.device, self.fields = torch.device(device), tuple(fields)
+        self.ragged, self.rank = self.host.ragged, rank
+        max_bytes = None if resident_max_gb is None else int(float(resident_max_gb) * 2 ** 30)
+        self.store = ResidentLatentStore(self.host.train_set.mapsets, self.device, self.fields, rank, world_size, max_bytes)
+        self.planner = EpochPlanner(self.store.lengths, batch_size, seq_len, max_per_map, max_len, pad_multiple, self.host.batch_frames,
+                                    self.host.bucket_pool)
+        self.feed = ResidentFeed(self.store, self.planner, self.ragged, rank)
+        self._val_store: Optional[ResidentLatentStore] = None
+        self._max_bytes = max_bytes
+
+    def train_dataloader(self) -> ResidentFeed:
+        return self.feed
+
+    def val_dataloader(self):
+        if self.store.has_frames:
+            return self.host.val_dataloader()
+        return self._style_val()
+
+    def _style_val(self) -> Iterator:
+        """Batch-1 tuples (empty h, empty z, s (1, S), labels (1, 5)) over the held-out maps, from a style store of their own."""
+        if self._val_store is None:
+            self._val_store = ResidentLatentStore(self.host.val_set.mapsets, self.device, STYLE_FIELDS, max_bytes=self._max_bytes)
+        vs = self._val_store
+        empty = torch.empty(1, 0, 1, dtype=torch.float32, device=self.device)
+        for i in range(len(vs)):
+            yield empty, empty, vs.s[i:i + 1], vs.labels[i:i + 1]
