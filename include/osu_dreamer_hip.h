@@ -113,6 +113,24 @@ int od_cl_to_frames(int dtype, const float* src, void* dst, int ldd, int B, int 
  * host loader's load, crop, zero-padded collate and host-to-device copy of a batch. */
 int od_feed_gather(const float* store, long store_elems, const long* base, const long* cstride, const int* lens, float* out,
                    int N, int C, int Lpad, void* stream);
+/* The same gather from a store of UNSIGNED INTEGERS of elem_size (1 or 2) bytes, dequantised on the way: the pre-processed dataset's
+ * spectrograms (uint8), hit signals (uint8) and cursor positions (uint16) stay in device memory as they lie in their files, and one launch
+ * per array fills C of the Ctot channels of a padded fp32 batch out[N][Ctot][Lpad], from channel c0 on (two launches fill one chart:
+ * c0 = 0, C = 7 from the hits and c0 = 7, C = 2 from the cursor; no concatenation follows).  base / cstride count ELEMENTS of elem_size.
+ *   q = store[base[n] + c * cstride[n] + l],  qmax = 255 or 65535
+ *   v = float( double(q) / qmax * scale[n][c] + offset[n][c] )            (scale, offset: device fp64 [N][C]; both NULL: double(q) / qmax)
+ *   out[n][c0 + c][l] = l < lens[n] ? (bit c of flip[n] ? 1.0f - v : v) : 0              (flip: device int32 [N], C <= 32; NULL: no flip)
+ * The divide, the multiply and the add are fp64 operations rounded one by one (no fused multiply-add), one rounding to fp32 follows, and
+ * the flip is fp32 arithmetic on the rounded value: the bits numpy and torch give the host loader.  Zeros are selected: a flipped padding
+ * frame is 0.  No byte outside [0, store_bytes) is loaded (bytes of the store behind a row's last frame may be: rows are read as aligned
+ * dwords); a row whose descriptor does not lie inside the store, or whose lens[n] is outside 1..Lpad, comes back as NaN and nothing is
+ * loaded for it.  OD_ERR_ARG: a null store / base / cstride / lens / out, only one of scale and offset, N, C, Lpad or store_bytes < 1,
+ * elem_size other than 1 or 2, c0 < 0 or c0 + C > Ctot, flip with C > 32.
+ * replaces: data/load_audio.py:58-59 and data/beatmap/encode.py:81-87 (integers -> [0, 1] -> cursor range) with the window slices, the
+ * x / y flip augmentation and the batch collate of data/modules/beatmap.py:119-207, and the host-to-device copy of the batch. */
+int od_feed_gather_quant(const void* store, long store_bytes, int elem_size, const long* base, const long* cstride, const int* lens,
+                         const double* scale, const double* offset, const int* flip, float* out, int N, int C, int c0, int Ctot,
+                         int Lpad, void* stream);
 /* x[m][c] = sum_e W[c][e] xt[b][e][l] + bias[c].  replaces: model.py:95 (proj_in). */
 int od_proj_in(int dtype, const float* xt, const float* W, const float* bias, void* x, int ldx, int B, int E, int L,
                int D, void* stream);

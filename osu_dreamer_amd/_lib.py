@@ -24,7 +24,7 @@ _CTYPES = {
     "int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float,
     "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
     "float*": ctypes.c_void_p, "const float*": ctypes.c_void_p,
-    "const int*": ctypes.c_void_p, "const long*": ctypes.c_void_p, "void**": ctypes.POINTER(ctypes.c_void_p),
+    "const int*": ctypes.c_void_p, "const long*": ctypes.c_void_p, "const double*": ctypes.c_void_p, "void**": ctypes.POINTER(ctypes.c_void_p),
     "const char*": ctypes.c_char_p,
     "long*": ctypes.POINTER(ctypes.c_long), "int*": ctypes.POINTER(ctypes.c_int), "double*": ctypes.POINTER(ctypes.c_double),
 }

@@ -72,6 +72,96 @@ __global__ __launch_bounds__(256) void feed_gather_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------ resident feed: quantised store -> padded fp32 (N, Ctot, Lpad) batch
+// The same wave-per-segment shape as feed_gather_kernel, reading unsigned integers of ES bytes and writing fp32: four bytes stored for
+// every byte read, so the stores set the pace.  A lane owns four consecutive frames and stores them as one 16-byte access when the row's
+// destination is 16-byte aligned.  Its four codes come from ALIGNED dwords of the store, shifted into place by the row's (wave-uniform)
+// byte residue: a window starts at any frame, so its source is dword-aligned one time in four, and four byte loads per 16-byte store would
+// make the loads the longer instruction stream.  The dword path runs only where the quad lies below len and its dwords lie inside the
+// store; the quad that straddles len, the dwords at the store's last bytes and every row whose destination is not aligned go element by
+// element under l < len, so no byte outside the store is ever loaded.
+//
+// The value is the host loader's, bit for bit: numpy divides, scales and shifts in float64, each operation rounded, and torch rounds to
+// fp32 once (.float()); the flip is fp32 arithmetic on that result.  Hence no contraction here: a fused multiply-add would skip a rounding.
+__device__ __forceinline__ float fq_value(unsigned q, double qmax, bool affine, double sc, double of, bool flip) {
+#pragma clang fp contract(off)
+    double v = (double)q / qmax;
+    if (affine) {
+        v = v * sc;
+        v = v + of;
+    }
+    const float f = (float)v;
+    return flip ? 1.0f - f : f;
+}
+
+template <int ES>
+__global__ __launch_bounds__(256) void feed_gather_quant_kernel(const unsigned char* __restrict__ store, long store_bytes, const long* __restrict__ base,
+                                                                const long* __restrict__ cstride, const int* __restrict__ lens,
+                                                                const double* __restrict__ scale, const double* __restrict__ offset,
+                                                                const int* __restrict__ flipmask, float* __restrict__ out, int C, int c0, int Ctot,
+                                                                int Lpad, int nseg, long items) {
+    typedef typename std::conditional<ES == 1, unsigned char, unsigned short>::type Q;
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
+    if (w >= items) return;
+    const long row = w / nseg;
+    const int seg = (int)(w - row * nseg);
+    const int n = (int)(row / C), c = (int)(row - (long)n * C);
+    const long store_elems = store_bytes / ES;
+    const long b0 = base[n], cs = cstride[n];
+    int len = lens[n];
+    // b0, cs <= store_elems first: c * cs cannot overflow for a descriptor that passes (C < 2^31, store_elems < 2^62 / C in any real store)
+    const bool sane = len >= 1 && len <= Lpad && b0 >= 0 && cs >= 0 && b0 <= store_elems && cs <= store_elems;
+    const long s0 = sane ? b0 + (long)c * cs : 0;
+    const bool ok = sane && s0 >= 0 && s0 <= store_elems - len;
+    const float fill = ok ? 0.f : __builtin_nanf("");
+    if (!ok) len = 0;
+    const double qmax = ES == 1 ? 255.0 : 65535.0;
+    const bool affine = scale != nullptr;
+    const double sc = affine ? scale[(long)n * C + c] : 1.0, of = affine ? offset[(long)n * C + c] : 0.0;
+    const bool flip = flipmask != nullptr && ((flipmask[n] >> c) & 1);
+    const Q* src = (const Q*)store + s0;                    // dereferenced under l < len only
+    float* dst = out + ((long)n * Ctot + c0 + c) * Lpad;
+    const int l0 = seg * FG_SEG;
+    const int l1 = l0 + FG_SEG < Lpad ? l0 + FG_SEG : Lpad;
+    if ((Lpad & 3) == 0 && (((size_t)dst) & 15) == 0 && (((size_t)store) & 3) == 0) {
+        const unsigned* s32 = (const unsigned*)store;
+        const long sbyte = s0 * ES;
+        const int sh = 8 * (int)(sbyte & 3);                // 0, 8, 16 or 24 bits (ES 2: 0 or 16): the same for every quad of the row
+        const long last = (store_bytes >> 2) - (sh ? ES + 1 : ES);      // the highest first dword whose ES (+ 1) dwords lie inside the store
+        for (int l = l0 + lane * 4; l < l1; l += 256) {     // Lpad % 4 == 0: a quad that starts below l1 ends at or below it
+            unsigned q[4];
+            const long a = (sbyte + (long)l * ES) >> 2;
+            if (l + 4 <= len && a <= last) {
+                unsigned d[ES + 1];
+#pragma unroll
+                for (int i = 0; i < ES; i++) d[i] = s32[a + i];
+                d[ES] = sh ? s32[a + ES] : 0u;
+#pragma unroll
+                for (int i = 0; i < ES; i++) d[i] = (unsigned)((((unsigned long)d[i + 1] << 32) | d[i]) >> sh);
+#pragma unroll
+                for (int e = 0; e < 4; e++) q[e] = ES == 1 ? (d[0] >> (8 * e)) & 255u : (d[e >> 1] >> (16 * (e & 1))) & 65535u;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) q[e] = l + e < len ? (unsigned)src[l + e] : 0u;
+            }
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[e] = l + e < len ? fq_value(q[e], qmax, affine, sc, of, flip) : fill;
+            *(f32x4*)(dst + l) = v;
+        }
+    } else {
+        for (int l = l0 + lane; l < l1; l += 256) {
+            unsigned q[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) q[e] = l + 64 * e < len ? (unsigned)src[l + 64 * e] : 0u;
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (l + 64 * e < l1) dst[l + 64 * e] = l + 64 * e < len ? fq_value(q[e], qmax, affine, sc, of, flip) : fill;
+        }
+    }
+}
+
 // ------------------------------------------------------------ proj_in: E (<=8) channels -> D
 template <class T>
 __global__ __launch_bounds__(256) void proj_in_kernel(const float* __restrict__ xt, const float* __restrict__ W,
@@ -544,6 +634,25 @@ extern "C" int od_feed_gather(const float* store, long store_elems, const long* 
     const long items = (long)N * C * nseg, blocks = (items + 3) / 4;
     if (blocks > 0x7fffffffL) return OD_ERR_UNSUPPORTED;
     OD_LAUNCH(feed_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, store, store_elems, base, cstride, lens, out, C, Lpad, nseg, items);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_feed_gather_quant(const void* store, long store_bytes, int elem_size, const long* base, const long* cstride, const int* lens,
+                                    const double* scale, const double* offset, const int* flip, float* out, int N, int C, int c0, int Ctot,
+                                    int Lpad, void* stream) {
+    if (!store || !base || !cstride || !lens || !out || Lpad < 1 || N < 1 || C < 1 || store_bytes < 1) return OD_ERR_ARG;
+    if ((elem_size != 1 && elem_size != 2) || (scale == nullptr) != (offset == nullptr)) return OD_ERR_ARG;
+    if (c0 < 0 || C > Ctot - c0 || (flip && C > 32)) return OD_ERR_ARG;
+    const int nseg = (Lpad + FG_SEG - 1) / FG_SEG;
+    const long items = (long)N * C * nseg, blocks = (items + 3) / 4;
+    if (blocks > 0x7fffffffL) return OD_ERR_UNSUPPORTED;
+    if (elem_size == 1)
+        OD_LAUNCH(feed_gather_quant_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)store, store_bytes, base,
+                  cstride, lens, scale, offset, flip, out, C, c0, Ctot, Lpad, nseg, items);
+    else
+        OD_LAUNCH(feed_gather_quant_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)store, store_bytes, base,
+                  cstride, lens, scale, offset, flip, out, C, c0, Ctot, Lpad, nseg, items);
     OD_CHECK_LAUNCH();
     return 0;
 }

@@ -466,9 +466,30 @@ def build_latent_from_config(cfg: Dict[str, Any]):
     return module, trainer
 
 
+def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer"):
+    """fit-latent's `data:` block -> its data module.  `data.resident: true` keeps the training set on the device as the integers of its
+    files (resident.py: every spec.npy and map read once, batches dequantised, flipped and padded by od_feed_gather_quant), within
+    `data.resident_max_gb` when that is set."""
+    from .data import BeatmapDataModule
+    resident, max_gb = data.pop("resident", False), data.pop("resident_max_gb", None)
+    if not resident:
+        if max_gb is not None:
+            raise ValueError("data.resident_max_gb bounds the resident store: set data.resident: true, or drop the key")
+        return BeatmapDataModule(**data)
+    from .resident import ResidentBeatmapDataModule
+    if data.get("num_workers") and trainer.rank == 0:
+        print(f"data.resident: batches are gathered on the device, data.num_workers={data['num_workers']} is ignored for training")
+    if torch.cuda.is_available():
+        device = torch.device("cuda", trainer.local_rank)
+    elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
+        device = torch.device("cpu")         # test-suite only, as in Trainer.fit
+    else:
+        raise RuntimeError("data.resident needs an MI355X: the store lives in device memory")
+    return ResidentBeatmapDataModule(**data, device=device, resident_max_gb=max_gb)
+
+
 def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
     """begin a training run for the latent model (reference: scripts/fit_latent.py, models/latent/model.yml)."""
-    from .data import BeatmapDataModule
     with open(config) as f:
         cfg = yaml.safe_load(f)
     for k, v in overrides.items():
@@ -477,7 +498,7 @@ def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = N
     if cfg.get("seed_everything") not in (None, False):
         seed_everything(cfg["seed_everything"])
     module, trainer = build_latent_from_config(cfg)
-    data = BeatmapDataModule(**cfg["data"])
+    data = build_beatmap_data(dict(cfg["data"]), trainer)
     trainer.fit(module, data, ckpt_path=ckpt_path)
     return module, trainer
 

@@ -181,6 +181,28 @@ def feed_gather(store, base, cstride, lens, out):
     _lib.lib().od_feed_gather(_p(store), store.numel(), _p(base), _p(cstride), _p(lens), _p(out), N, C, Lpad, _stream(out))
 
 
+def feed_gather_quant(store, elem_size, base, cstride, lens, out, c0=0, channels=None, scale=None, offset=None, flip=None):
+    """Channels c0 .. c0 + channels of out (N, Ctot, Lpad) fp32 = per row n, lens[n] frames of `channels` channels of unsigned integers of
+    `elem_size` (1 or 2) bytes from the byte `store` (uint8, flat) at element base[n] + c * cstride[n], as double(q) / qmax * scale[n][c] +
+    offset[n][c] rounded once to fp32 (scale / offset: device fp64 (N, channels), or both None), then 1 - v where bit c of flip[n] (device
+    int32 [N], or None) is set; zero beyond lens[n].  Every element of those channels is written, no other."""
+    N, Ctot, Lpad = out.shape
+    C = Ctot - c0 if channels is None else channels
+    _f32(out)
+    _lens(lens, N)
+    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous(), "the store is a flat uint8 tensor (its bytes)"
+    for t in (base, cstride):
+        assert t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == N and t.is_contiguous(), "base / cstride must be contiguous int64 [N]"
+    assert (scale is None) == (offset is None), "scale and offset come together"
+    for t in (scale, offset):
+        assert t is None or (t.dtype == torch.float64 and tuple(t.shape) == (N, C) and t.is_contiguous()), "scale / offset must be contiguous fp64 (N, channels)"
+    if flip is not None:
+        _lens(flip, N)
+    assert all(t is None or t.device == out.device for t in (store, base, cstride, lens, scale, offset, flip)), "feed_gather_quant: every tensor on one device"
+    _lib.lib().od_feed_gather_quant(_p(store), store.numel(), elem_size, _p(base), _p(cstride), _p(lens), _p(scale), _p(offset), _p(flip), _p(out),
+                                    N, C, c0, Ctot, Lpad, _stream(out))
+
+
 def proj_in(xt, W, bias, x):
     B, E, L = xt.shape
     D = x.shape[1]

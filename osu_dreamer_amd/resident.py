@@ -13,6 +13,12 @@ that would not, before anything is allocated.
 The feed follows the host loader's rules in its three modes (an integer seq_len: fixed windows; seq_len None with batch_size N: N whole
 maps per batch; batch_frames: frame-budget batches cut by data.cut_batches), with one difference that comes with planning a whole epoch at
 once: the order is a full permutation of the epoch's samples instead of a shuffle buffer's, so `shuffle_buffer_size` has no meaning here.
+
+The latent model's trainer has the same feed over the pre-processed beatmaps (the second half of this file): `BeatmapDataModule` opens the
+mapset's whole `spec.npy` and the map's npz for every sample of every epoch, widens both to float64 and keeps one window.  Here
+`ResidentBeatmapStore` keeps the files' unsigned integers on the device (spec once per mapset, hit and xy per map), the same `EpochPlanner`
+plans the windows, `ResidentBeatmapFeed` draws their flips, and `od_feed_gather_quant` dequantises, places, flips and pads a batch in three
+launches — bit for bit the host loader's float32 values.
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .data import NUM_LABELS, LatentBatch, LatentDataModule, LatentDataset, RaggedLatentBatch, cut_batches
+from .data import (A_DIM, NUM_LABELS, X_DIM, Batch, BeatmapDataModule, BeatmapDataset, LatentBatch, LatentDataModule, LatentDataset,
+                   RaggedLatentBatch, cut_batches)
 
 ALL_FIELDS = ("h", "z", "s", "labels")
 STYLE_FIELDS = ("s", "labels")
@@ -34,22 +41,33 @@ def _roundup(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
+def _read_header(f) -> Tuple[Tuple[int, ...], np.dtype]:
+    version = np.lib.format.read_magic(f)
+    read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+    shape, _, dtype = read(f)
+    return tuple(int(x) for x in shape), np.dtype(dtype)
+
+
+def npz_member_header(path, member: str) -> Tuple[Tuple[int, ...], np.dtype]:
+    """(shape, dtype) of `member` of an .npz, from the member's .npy header (the array is not read)."""
+    with zipfile.ZipFile(path) as z, z.open(member + ".npy") as f:
+        return _read_header(f)
+
+
+def npy_header(path) -> Tuple[Tuple[int, ...], np.dtype]:
+    """(shape, dtype) of an .npy file, from its header (the array is not read or mapped)."""
+    with open(path, "rb") as f:
+        return _read_header(f)
+
+
 def npz_member_shape(path, member: str) -> Tuple[int, ...]:
     """Shape of `member` of an .npz, from the member's .npy header (the array is not read)."""
-    with zipfile.ZipFile(path) as z, z.open(member + ".npy") as f:
-        version = np.lib.format.read_magic(f)
-        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
-        shape, _, _ = read(f)
-    return tuple(int(x) for x in shape)
+    return npz_member_header(path, member)[0]
 
 
 def npy_shape(path) -> Tuple[int, ...]:
     """Shape of an .npy file, from its header (the array is not read or mapped)."""
-    with open(path, "rb") as f:
-        version = np.lib.format.read_magic(f)
-        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
-        shape, _, _ = read(f)
-    return tuple(int(x) for x in shape)
+    return npy_header(path)[0]
 
 
 def shard_files(mapsets: Sequence[Path], rank: int = 0, world_size: int = 1) -> List[Path]:
@@ -232,20 +250,21 @@ class ResidentLatentStore:
 
 
 class _Uploader:
-    """Host arrays -> slices of a flat device tensor through two pinned staging buffers used in turn (a buffer is refilled only after the
-    copy that read it has finished).  On the host (the test-suite's emulator backend) a plain copy."""
+    """Host arrays -> slices of a flat device tensor of `dtype` through two pinned staging buffers used in turn (a buffer is refilled only
+    after the copy that read it has finished).  On the host (the test-suite's emulator backend) a plain copy."""
 
-    def __init__(self, device, staging_bytes: int):
+    def __init__(self, device, staging_bytes: int, dtype: torch.dtype = torch.float32):
         self.cuda = device.type == "cuda"
+        self.np_dtype = torch.empty(0, dtype=dtype).numpy().dtype
         if self.cuda:
-            k = max(1, staging_bytes // 4)
-            self.bufs = [torch.empty(k, dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            k = max(1, staging_bytes // self.np_dtype.itemsize)
+            self.bufs = [torch.empty(k, dtype=dtype, pin_memory=True) for _ in range(2)]
             self.events = [None, None]
             self.turn = 0
             self.stream = torch.cuda.current_stream(device)
 
     def put(self, dst: torch.Tensor, off: int, arr: np.ndarray):
-        flat = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+        flat = np.ascontiguousarray(arr, dtype=self.np_dtype).reshape(-1)
         if not self.cuda:
             dst[off:off + flat.size].copy_(torch.from_numpy(flat))
             return
@@ -360,3 +379,185 @@ class ResidentLatentDataModule:
         empty = torch.empty(1, 0, 1, dtype=torch.float32, device=self.device)
         for i in range(len(vs)):
             yield empty, empty, vs.s[i:i + 1], vs.labels[i:i + 1]
+
+
+# ------------------------------------------------------------------------------------------- the latent model's feed: quantised beatmaps
+HIT_DIM = X_DIM - 2                    # chart rows 0..6 come from `hit` (uint8), rows 7, 8 (cursor x, y) from `xy` (uint16)
+FLIP_X, FLIP_Y = 1, 2                  # bits of a window's flip mask = bits of od_feed_gather_quant's mask over the two xy channels
+
+
+class BeatmapPlanBatch(NamedTuple):
+    """PlanBatch of fixed windows with each window's flip augmentation: bit FLIP_X / FLIP_Y of flips[i] set = cursor x / y of row i is
+    mirrored (v <- 1 - v), each with probability 1/2 (BeatmapDataset.make_samples)."""
+    maps: np.ndarray       # (B,) int64
+    starts: np.ndarray     # (B,) int64
+    lens: np.ndarray       # (B,) int64
+    Lpad: int
+    flips: np.ndarray      # (B,) int32
+
+
+class ResidentBeatmapStore:
+    """The rank's share of a pre-processed beatmap dataset on `device`, every file read once and kept AS STORED — unsigned integers:
+
+      data      flat uint8: every mapset's `spec.npy` (72, Ls) once, then every map's `hit` (7, L), then every map's `xy` (2, L) uint16 at a
+                4-byte-aligned byte offset, each array as it lies in its file (channel-major)
+      spec_base / spec_stride / hit_base / xy_base / lengths  (host int64, one per map): channel c of map m's spectrogram starts at byte
+                spec_base[m] + c * spec_stride[m] (maps of one mapset share the values), of its hit at byte hit_base[m] + c * lengths[m], of
+                its xy at uint16 ELEMENT xy_base[m] + c * lengths[m]
+      xy_rng / xy_min  (n_maps, 2) fp64 on the host: they travel with each batch's descriptors (od_feed_gather_quant's scale / offset)
+      labels    (n_maps, 5) fp32 on the device: a table for torch.index_select
+      lengths   chart frames per map, on the host: all an epoch plan needs
+
+    A 30 000-frame mapset takes 2.2 MB plus 0.33 MB per difficulty: 11 bytes per chart frame against the 324 a float32 batch spends.
+    Every size and dtype is read from the files' headers first; `max_bytes`: refuse — before anything is allocated — a store that needs
+    more.  The upload goes through two pinned staging buffers of `staging_bytes` each."""
+
+    def __init__(self, mapsets: Sequence[Path], device, rank: int = 0, world_size: int = 1, max_bytes: Optional[int] = None,
+                 staging_bytes: int = 32 << 20):
+        self.device = torch.device(device)
+        self.files = [f for i, f in enumerate(BeatmapDataset(list(mapsets))._files()) if i % world_size == rank]
+        if not self.files:
+            raise ValueError(f"no *.map.npy file for rank {rank} of {world_size}")
+        n = len(self.files)
+        # ---- sizes and dtypes from the headers
+        self.lengths = np.zeros(n, dtype=np.int64)
+        self.spec_base, self.spec_stride = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        self.hit_base, self.xy_base = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        spec_files: List[Tuple[Path, int]] = []                # (mapset's spec.npy, its byte offset), each once
+        seen = {}
+        nbytes = 0
+        for i, f in enumerate(self.files):
+            (hit_shape, hit_dt), (xy_shape, xy_dt) = npz_member_header(f, "hit"), npz_member_header(f, "xy")
+            if hit_dt != np.uint8 or xy_dt != np.uint16:
+                raise ValueError(f"{f}: hit is {hit_dt} and xy is {xy_dt}; the resident store keeps hit as uint8 and xy as uint16, as the "
+                                 "pre-processing writes them")
+            L = hit_shape[-1]
+            if hit_shape != (HIT_DIM, L) or xy_shape != (2, L):
+                raise ValueError(f"{f}: hit {hit_shape} / xy {xy_shape}, expected ({HIT_DIM}, L) / (2, L)")
+            self.lengths[i] = L
+            d = f.parent
+            if d not in seen:
+                spec = d / "spec.npy"
+                shape, dt = npy_header(spec)
+                if dt != np.uint8:
+                    raise ValueError(f"{spec}: dtype {dt}; the resident store keeps spectrograms as uint8, as the pre-processing writes them")
+                if len(shape) != 2 or shape[0] != A_DIM:
+                    raise ValueError(f"{spec}: shape {shape}, expected ({A_DIM}, frames)")
+                seen[d] = (nbytes, shape[1])
+                spec_files.append((spec, nbytes))
+                nbytes += A_DIM * shape[1]
+            self.spec_base[i], self.spec_stride[i] = seen[d]
+            if self.spec_stride[i] < L:
+                raise ValueError(f"{d / 'spec.npy'}: {self.spec_stride[i]} frames, shorter than its map {f.name} ({L} frames)")
+        for i in range(n):
+            self.hit_base[i] = nbytes
+            nbytes += HIT_DIM * int(self.lengths[i])
+        for i in range(n):
+            nbytes = _roundup(nbytes, 4)
+            self.xy_base[i] = nbytes // 2
+            nbytes += 2 * 2 * int(self.lengths[i])
+        self.nbytes = nbytes + 4 * n * NUM_LABELS
+        if max_bytes is not None and self.nbytes > max_bytes:
+            raise MemoryError(f"the resident store needs {self.nbytes} bytes ({self.nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than the limit of "
+                              f"{int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or train with data.resident: false")
+        # ---- allocate and fill
+        self.data = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.xy_rng, self.xy_min = np.empty((n, 2), dtype=np.float64), np.empty((n, 2), dtype=np.float64)
+        labels_host = np.empty((n, NUM_LABELS), dtype=np.float32)
+        up = _Uploader(self.device, staging_bytes, torch.uint8)
+        for path, off in spec_files:
+            up.put(self.data, off, np.load(path))
+        for i, f in enumerate(self.files):
+            with np.load(f) as d:
+                up.put(self.data, int(self.hit_base[i]), d["hit"])
+                up.put(self.data, 2 * int(self.xy_base[i]), np.ascontiguousarray(d["xy"]).view(np.uint8))
+                self.xy_rng[i], self.xy_min[i] = np.asarray(d["xy_rng"], dtype=np.float64).reshape(2), np.asarray(d["xy_min"], dtype=np.float64).reshape(2)
+                labels_host[i] = np.asarray(d["labels"]).reshape(-1)
+        up.finish()
+        self.labels = torch.from_numpy(labels_host).to(self.device)
+
+    def __len__(self):
+        return len(self.files)
+
+
+class ResidentBeatmapFeed:
+    """Re-iterable over the batches of one epoch each, as ResidentFeed: every iter() draws a new plan — the windows by EpochPlanner's
+    fixed-window rule on the chart lengths (BeatmapDataset.make_samples' rule), then the two flips of every window — from the feed's
+    generator, seeded at the first epoch like the host dataset (torch.initial_seed() + 7919 * rank), and yields `data.Batch`es built on the
+    device by three od_feed_gather_quant launches."""
+
+    def __init__(self, store: ResidentBeatmapStore, planner: EpochPlanner, rank: int = 0):
+        if planner.seq_len is None:
+            raise ValueError("the resident beatmap feed cuts fixed windows: it needs an integer seq_len")
+        self.store, self.planner, self.rank = store, planner, rank
+        self.gen: Optional[torch.Generator] = None
+        self.pin = store.device.type == "cuda"
+
+    def plan_epoch(self) -> List[BeatmapPlanBatch]:
+        if self.gen is None:
+            self.gen = torch.Generator().manual_seed(torch.initial_seed() + 7919 * self.rank)
+        plan = self.planner.plan(self.gen)
+        B = self.planner.batch_size
+        draws = (torch.rand(len(plan) * B, 2, generator=self.gen) < 0.5).numpy()
+        flips = (draws[:, 0] * FLIP_X + draws[:, 1] * FLIP_Y).astype(np.int32)
+        return [BeatmapPlanBatch(pb.maps, pb.starts, pb.lens, pb.Lpad, flips[i * B:(i + 1) * B]) for i, pb in enumerate(plan)]
+
+    def gather(self, pb: BeatmapPlanBatch) -> Batch:
+        """The device batch of one plan entry.  Everything the three launches read per row travels as ONE stream-ordered copy from pinned
+        memory, 11 B 64-bit words: the spectrogram's base and channel stride, the hit and xy bases, the chart's channel stride, the map
+        index (for the labels), xy_rng and xy_min as fp64 (B, 2) each, then the lengths and the flip masks as int32."""
+        st, B, T = self.store, len(pb.maps), pb.Lpad
+        # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
+        assert (pb.starts >= 0).all() and (pb.lens >= 1).all() and (pb.lens <= T).all() and (pb.starts + pb.lens <= st.lengths[pb.maps]).all()
+        host = torch.empty(11 * B, dtype=torch.int64, pin_memory=self.pin)
+        hv = host.numpy()
+        hv[0:B], hv[B:2 * B] = st.spec_base[pb.maps] + pb.starts, st.spec_stride[pb.maps]
+        hv[2 * B:3 * B], hv[3 * B:4 * B] = st.hit_base[pb.maps] + pb.starts, st.xy_base[pb.maps] + pb.starts
+        hv[4 * B:5 * B], hv[5 * B:6 * B] = st.lengths[pb.maps], pb.maps
+        hv[6 * B:8 * B].view(np.float64)[:] = st.xy_rng[pb.maps].reshape(-1)
+        hv[8 * B:10 * B].view(np.float64)[:] = st.xy_min[pb.maps].reshape(-1)
+        i32 = hv[10 * B:].view(np.int32)
+        i32[:B], i32[B:] = pb.lens, pb.flips
+        desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
+        desc.copy_(host, non_blocking=True)
+        rng, lo = desc[6 * B:8 * B].view(torch.float64).view(B, 2), desc[8 * B:10 * B].view(torch.float64).view(B, 2)
+        d32 = desc[10 * B:].view(torch.int32)
+        lens32, flips = d32[:B], d32[B:]
+        audio = torch.empty(B, A_DIM, T, dtype=torch.float32, device=st.device)
+        chart = torch.empty(B, X_DIM, T, dtype=torch.float32, device=st.device)
+        ops.feed_gather_quant(st.data, 1, desc[0:B], desc[B:2 * B], lens32, audio)
+        ops.feed_gather_quant(st.data, 1, desc[2 * B:3 * B], desc[4 * B:5 * B], lens32, chart, c0=0, channels=HIT_DIM)
+        ops.feed_gather_quant(st.data, 2, desc[3 * B:4 * B], desc[4 * B:5 * B], lens32, chart, c0=HIT_DIM, channels=2, scale=rng, offset=lo, flip=flips)
+        return Batch(audio, chart, st.labels.index_select(0, desc[5 * B:6 * B]))
+
+    def __iter__(self) -> Iterator[Batch]:
+        for pb in self.plan_epoch():
+            yield self.gather(pb)
+
+
+class ResidentBeatmapDataModule:
+    """`BeatmapDataModule` with the training set resident on `device`: the same constructor keys (the YAML `data:` block of fit-latent)
+    plus `device` and `resident_max_gb`.  The host module holds out the validation mapsets and keeps the validation loader (validation
+    reads whole maps once per check), which is all `num_workers` still serves; `shuffle_buffer_size` serves nothing: an epoch is a full
+    permutation of its windows."""
+
+    def __init__(self, batch_size: int, seq_len: int, num_workers: int = 0, max_val_count: int = 512, max_val_frac: float = .3,
+                 data_path: str = "./data", shuffle_buffer_size: int = 1, max_per_map: int = -1, rank: int = 0, world_size: int = 1,
+                 device=None, resident_max_gb: Optional[float] = None):
+        if seq_len is None:
+            raise ValueError("data.resident trains fit-latent on fixed windows: data.seq_len must be an integer")
+        self.host = BeatmapDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
+                                      rank, world_size)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.device, self.rank = torch.device(device), rank
+        max_bytes = None if resident_max_gb is None else int(float(resident_max_gb) * 2 ** 30)
+        self.store = ResidentBeatmapStore(self.host.train_set.mapsets, self.device, rank, world_size, max_bytes)
+        self.planner = EpochPlanner(self.store.lengths, batch_size, int(seq_len), max_per_map)
+        self.feed = ResidentBeatmapFeed(self.store, self.planner, rank)
+
+    def train_dataloader(self) -> ResidentBeatmapFeed:
+        return self.feed
+
+    def val_dataloader(self):
+        return self.host.val_dataloader()
