@@ -131,6 +131,10 @@ int od_feed_gather(const float* store, long store_elems, const long* base, const
 int od_feed_gather_quant(const void* store, long store_bytes, int elem_size, const long* base, const long* cstride, const int* lens,
                          const double* scale, const double* offset, const int* flip, float* out, int N, int C, int c0, int Ctot,
                          int Lpad, void* stream);
+/* Replicate padding behind the rows of a gathered fp32 batch x[N][C][Lpad]: x[n][c][l] = x[n][c][lens[n] - 1] for lens[n] <= l < plens[n]
+ * (lens, plens: device int32 [N]); nothing else is written.  A row with lens[n] < 1 or plens[n] > Lpad comes back as NaN.
+ * OD_ERR_ARG: a null pointer, N, C or Lpad < 1.  replaces: data/modules/beatmap.py:26-30 (F.pad(mode="replicate") of a whole map). */
+int od_replicate_tail(float* x, const int* lens, const int* plens, int N, int C, int Lpad, void* stream);
 /* x[m][c] = sum_e W[c][e] xt[b][e][l] + bias[c].  replaces: model.py:95 (proj_in). */
 int od_proj_in(int dtype, const float* xt, const float* W, const float* bias, void* x, int ldx, int B, int E, int L,
                int D, void* stream);
@@ -527,6 +531,34 @@ int od_latent_loss(const float* logits, const float* chart, const float* pred_la
 int od_latent_loss_bwd(const float* logits, const float* chart, const float* pred_labels, const float* true_labels, const void* masked,
                        const float* coef, const float* g, float* dlogits, float* dlabels, float* ds_reg, int B2, int L,
                        float s_reg_weight, void* stream);
+
+/* ---- validation of the latent model over ragged groups of whole maps (eval only, fp32, no gradient): map g of a group owns rows 2g
+ *      and 2g + 1 of the half batch.  Same conventions as above: per-block partial rows in `ws`, a second pass in fixed order, no
+ *      atomics, the same bits from launch to launch. ---- */
+/* out[g][0:4] = (MMD^2, zz, pp, zp) of rows 2g, 2g + 1 of s [2G][S] against the same rows of prior: the bits of od_mmd_imq with N = 2 on
+ * those two rows.  S <= 256; ws: 6 G floats.  replaces: common/wae.py:4-28 at latent/train.py:88, once per validation map. */
+int od_mmd_imq_pairs(const float* s, const float* prior, float* out, float* ws, long ws_floats, int G, int S, void* stream);
+/* out[g][0:13] = the 13 values of od_latent_loss(training = 0, B2 = 2, L = hlens[2g], nothing masked, s_reg = s_reg[g * s_reg_stride]) on
+ * rows 2g and 2g + 1 of logits / chart (2G, 9, Hmax), pred_labels / true_labels [2G][5], bit for bit: the same tiles of
+ * od_latent_loss_block_frames() frames, row 2g's tile partials before row 2g + 1's, added as od_latent_loss adds them.  hlens: device
+ * int32 [2G]; frames at or past hlens[b] are never loaded (padding may hold NaN).  loss_ema [11] is read, never written.  A map whose two
+ * lengths differ or lie outside 3..Hmax comes back as NaN.  ws: od_latent_loss_ws_floats(2G, Hmax) floats.
+ * replaces: latent/train.py:115-149 in validation, once per map. */
+int od_latent_loss_maps(const float* logits, const float* chart, const int* hlens, const float* pred_labels, const float* true_labels,
+                        const float* s_reg, int s_reg_stride, const float* loss_ema, float* out, float* ws, long ws_floats, int G,
+                        int Hmax, float s_reg_weight, void* stream);
+/* floats of `ws` for od_latent_eval_maps. */
+int od_latent_eval_maps_ws_floats(int G, int Pmax);
+/* The validation metrics of map g from its true chart and decoded pred_chart (G, 9, Pmax), valid for plens[g] frames, its latent
+ * z (G, E, lmax), valid for zlens[g] frames, and pred_labels / true_labels [G][5].  out[g][0:8] = sum t^2, sum p t, sum p^2 on the onset
+ * channel; the residual sum of squares of the cursor velocity (first differences of channels 7, 8 in pixels: x 512, x 384) and its total
+ * sum of squares about the per-channel mean of the true velocity over the map's plens[g] - 1 differences (the mean first, the squares in
+ * a second pass); mean |pixel error| over 2 plens[g] values; mean |label error|; the minimum over E of the unbiased variance of z over
+ * zlens[g] frames.  Nothing at or past plens / zlens is loaded; plens[g] outside 2..Pmax or zlens[g] outside 1..lmax: NaN.
+ * replaces: latent/train.py:210-255 (eval_metrics) and its five host reads per map. */
+int od_latent_eval_maps(const float* chart, const float* pred_chart, const int* plens, const float* z, const int* zlens,
+                        const float* pred_labels, const float* true_labels, float* out, float* ws, long ws_floats, int G, int Pmax, int E,
+                        int lmax, void* stream);
 
 /* ---- varlen forms of the latent kernels: G songs / maps stacked in the padded [B*L][C] layout; lens (device int32 [B]) = valid
  *      frames of sequence b at the level the call reads.  Taps and frames at or past lens[b] read as zero (selected, so padding may

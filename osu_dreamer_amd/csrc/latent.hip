@@ -1693,6 +1693,285 @@ __global__ __launch_bounds__(256) void latent_loss_grad_kernel(const float* __re
     }
 }
 
+// ---- validation over ragged groups of whole maps: the reductions above per map, eval only ------------------------------------------
+// Map g of a group owns rows 2g and 2g + 1 (its two halves).  Each kernel below is its whole-batch twin restricted to those two rows, with
+// the same tiles, the same partial rows and the same order of additions, so a map's values are the bits the twin gives on the two rows alone.
+
+// Block i: row i of z and of p against the two rows of its pair: mmd_rows_kernel with N = 2, without the gradient.
+__global__ __launch_bounds__(256) void mmd_pairs_rows_kernel(const float* __restrict__ z, const float* __restrict__ p, float* __restrict__ ws,
+                                                             int D) {
+    __shared__ float s_zi[MMD_DMAX], s_pi[MMD_DMAX], s_red[3][256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (tid < D) {
+        s_zi[tid] = z[(size_t)i * D + tid];
+        s_pi[tid] = p[(size_t)i * D + tid];
+    }
+    __syncthreads();
+    const float Cb = 2.f * (float)D;
+    float a_zz = 0.f, a_pp = 0.f, a_zp = 0.f;
+    if (tid < 2) {
+        const int j = (i & ~1) + tid;
+        float dzz = 0.f, dpp = 0.f, dzp = 0.f, unused;
+        for (int d = 0; d < D; d++) {
+            const float zj = z[(size_t)j * D + d], pj = p[(size_t)j * D + d];
+            const float a = s_zi[d] - zj, b = s_pi[d] - pj, c = s_zi[d] - pj;
+            dzz += a * a;
+            dpp += b * b;
+            dzp += c * c;
+        }
+        a_zp += imq7(dzp, Cb, unused);
+        if (j != i) {
+            a_zz += imq7(dzz, Cb, unused);
+            a_pp += imq7(dpp, Cb, unused);
+        }
+    }
+    s_red[0][tid] = a_zz;
+    s_red[1][tid] = a_pp;
+    s_red[2][tid] = a_zp;
+    block_tree_sum<3>(s_red);
+    if (tid < 3) ws[(size_t)i * 3 + tid] = s_red[tid][0];
+}
+
+// Block g: out[g] = (value, zz, pp, zp) of the pair, its two partial rows added as mmd_finalize_kernel adds them for N = 2
+__global__ __launch_bounds__(256) void mmd_pairs_finalize_kernel(const float* __restrict__ ws, float* __restrict__ out) {
+    __shared__ float s_red[3][256];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    float a[3] = {0.f, 0.f, 0.f};
+    if (tid < 2)
+        for (int k = 0; k < 3; k++) a[k] += ws[((size_t)2 * g + tid) * 3 + k];
+    for (int k = 0; k < 3; k++) s_red[k][tid] = a[k];
+    block_tree_sum<3>(s_red);
+    if (tid == 0) {
+        const float n = 2.f, zz = s_red[0][0] / (n * (n - 1.f)), pp = s_red[1][0] / (n * (n - 1.f)), zp = s_red[2][0] / (n * n);
+        out[g * 4 + 0] = zz + pp - 2.f * zp;
+        out[g * 4 + 1] = zz;
+        out[g * 4 + 2] = pp;
+        out[g * 4 + 3] = zp;
+    }
+}
+
+// Block (tile, b): latent_loss_sums_kernel on the first hlens[b] frames of row b of a batch padded to Hmax; a tile past the row's length
+// writes nothing (its partial row is never read) and no frame at or past hlens[b] is loaded.
+__global__ __launch_bounds__(256) void latent_loss_maps_sums_kernel(const float* __restrict__ logits, const float* __restrict__ chart,
+                                                                    const int* __restrict__ hlens, float* __restrict__ ws, int Hmax) {
+    __shared__ float s_red[LL_NS][256];
+    const int tid = threadIdx.x, b = blockIdx.y, L = hlens[b], l = blockIdx.x * LL_T + tid;
+    if (L < 3 || L > Hmax || (int)blockIdx.x * LL_T >= L) return;
+    const float* x = logits + (size_t)b * 9 * Hmax;
+    const float* y = chart + (size_t)b * 9 * Hmax;
+    float acc[LL_NS];
+#pragma unroll
+    for (int k = 0; k < LL_NS; k++) acc[k] = 0.f;
+    if (l < L) {
+#pragma unroll
+        for (int k = 0; k < LL_HIT; k++) {
+            const float v = x[(size_t)k * Hmax + l], t = y[(size_t)k * Hmax + l];
+            const float bce = fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
+            acc[k] = bce + (xlogx(t) + xlogx(1.f - t));
+        }
+        for (int c = LL_HIT; c < 9; c++) {
+            const float* xe = x + (size_t)c * Hmax;
+            const float* ye = y + (size_t)c * Hmax;
+            const float e0 = xe[l] - ye[l];
+            acc[7] += e0 * e0;
+            if (l + 1 < L) {
+                const float e1 = xe[l + 1] - ye[l + 1], d1 = e1 - e0;
+                acc[8] += d1 * d1;
+                if (l + 2 < L) {
+                    const float e2 = xe[l + 2] - ye[l + 2], d2 = (e2 - e1) - d1;
+                    acc[9] += d2 * d2;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < LL_NS; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<LL_NS>(s_red);
+    if (tid < LL_NS) ws[((size_t)b * gridDim.x + blockIdx.x) * LL_NS + tid] = s_red[tid][0];
+}
+
+// Block g: latent_loss_finalize_kernel for B2 = 2, L = hlens[2g], training = 0 and no row masked, on the partial rows of rows 2g and 2g + 1
+// (nbl of the nbl_max slots of each, row 2g's first).  loss_ema is read, never written.  A pair whose lengths differ or lie outside 3..Hmax
+// comes back as NaN.
+__global__ __launch_bounds__(256) void latent_loss_maps_finalize_kernel(const float* __restrict__ ws, int nbl_max, const int* __restrict__ hlens,
+                                                                        const float* __restrict__ pred_labels,
+                                                                        const float* __restrict__ true_labels, const float* __restrict__ s_reg,
+                                                                        int s_reg_stride, const float* __restrict__ loss_ema,
+                                                                        float* __restrict__ out, int Hmax, float s_reg_weight) {
+    __shared__ float s_red[LL_NS + 2][256];
+    const int tid = threadIdx.x, g = blockIdx.x, B2 = 2, L = hlens[2 * g];
+    if (L < 3 || L > Hmax || hlens[2 * g + 1] != L) {
+        if (tid < LL_NL + 2) out[g * (LL_NL + 2) + tid] = __builtin_nanf("");
+        return;
+    }
+    const int nbl = (L + LL_T - 1) / LL_T, nrows = B2 * nbl;
+    float acc[LL_NS + 2];
+#pragma unroll
+    for (int k = 0; k < LL_NS + 2; k++) acc[k] = 0.f;
+    for (int r = tid; r < nrows; r += 256) {
+        const int b = r / nbl, row = (2 * g + b) * nbl_max + (r - b * nbl);
+#pragma unroll
+        for (int k = 0; k < LL_NS; k++) acc[k] += ws[(size_t)row * LL_NS + k];
+    }
+    for (int b = tid; b < B2; b += 256) {
+        const float* pl = pred_labels + (size_t)(2 * g + b) * 5;
+        const float* tl = true_labels + (size_t)(2 * g + b) * 5;
+        float q = 0.f;
+        for (int j = 0; j < 5; j++) {
+            const float d = pl[j] - tl[j];
+            q += d * d;
+        }
+        acc[LL_NS] += q / 5.f;
+        acc[LL_NS + 1] += 1.f;
+    }
+#pragma unroll
+    for (int k = 0; k < LL_NS + 2; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<LL_NS + 2>(s_red);
+    if (tid == 0) {
+        const float wts[LL_NL] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 2.f, 2.f, 2.f, 2.f};
+        float n[LL_NL];
+        for (int k = 0; k < LL_HIT; k++) n[k] = (float)B2 * (float)L;
+        for (int k = 0; k < 3; k++) n[LL_HIT + k] = (float)B2 * 2.f * (float)(L - k);
+        n[10] = fmaxf(s_red[LL_NS + 1][0], 1.f);
+        float* o = out + (size_t)g * (LL_NL + 2);
+        const float sr = s_reg[(size_t)g * s_reg_stride];
+        float loss = 0.f;
+        for (int k = 0; k < LL_NL; k++) {
+            const float v = s_red[k][0] / n[k];
+            const float c = wts[k] / fmaxf(loss_ema[k], 1e-8f);
+            loss += c * v;
+            o[k] = v;
+        }
+        o[LL_NL] = sr;
+        o[LL_NL + 1] = loss + s_reg_weight * sr;
+    }
+}
+
+// ---- eval_metrics per map, latent/train.py:210-255 ---------------------------------------------------------------------------------
+constexpr int EV_T = 256;        // frames of one map a block of the first two passes owns
+constexpr int EV_NW = 8;         // floats of a tile's partial row: tt, pt, pp, residual, |pixel error|, sum of the true velocity (x, y), total
+
+// true / predicted velocity of channel c (7: x, 8: y) at frame l, in pixels: the difference first (exact for neighbouring positions), one
+// product after it
+__device__ __forceinline__ float ev_vel(const float* __restrict__ row, int l, float px) { return (row[l + 1] - row[l]) * px; }
+
+__device__ __forceinline__ bool ev_ok(int P, int Pmax) { return P >= 2 && P <= Pmax; }
+
+// Block (tile, g), pass 1: the tile's sums on the onset channel and the cursor channels, and the sum of the true velocity per channel
+__global__ __launch_bounds__(256) void latent_eval_sums_kernel(const float* __restrict__ chart, const float* __restrict__ pred,
+                                                               const int* __restrict__ plens, float* __restrict__ ws, int Pmax) {
+    __shared__ float s_red[7][256];
+    const int tid = threadIdx.x, g = blockIdx.y, P = plens[g], l = blockIdx.x * EV_T + tid;
+    if (!ev_ok(P, Pmax) || (int)blockIdx.x * EV_T >= P) return;
+    const float* y = chart + (size_t)g * 9 * Pmax;
+    const float* x = pred + (size_t)g * 9 * Pmax;
+    float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (l < P) {
+        const float t = y[l], p = x[l];                     // channel 0: the onset signal
+        acc[0] = t * t;
+        acc[1] = p * t;
+        acc[2] = p * p;
+        for (int c = 0; c < 2; c++) {
+            const float px = c == 0 ? 512.f : 384.f;
+            const float* ye = y + (size_t)(LL_HIT + c) * Pmax;
+            const float* xe = x + (size_t)(LL_HIT + c) * Pmax;
+            acc[4] += fabsf((xe[l] - ye[l]) * px);
+            if (l + 1 < P) {
+                const float tv = ev_vel(ye, l, px), r = ev_vel(xe, l, px) - tv;
+                acc[3] += r * r;
+                acc[5 + c] = tv;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<7>(s_red);
+    if (tid < 7) ws[((size_t)g * gridDim.x + blockIdx.x) * EV_NW + tid] = s_red[tid][0];
+}
+
+// Block (tile, g), pass 2: the mean true velocity of the map per channel from pass 1's partial rows (every block of a map adds them in
+// the same order), then the tile's squares about it
+__global__ __launch_bounds__(256) void latent_eval_total_kernel(const float* __restrict__ chart, const int* __restrict__ plens,
+                                                                float* __restrict__ ws, int Pmax) {
+    __shared__ float s_red[2][256];
+    const int tid = threadIdx.x, g = blockIdx.y, P = plens[g], l = blockIdx.x * EV_T + tid;
+    if (!ev_ok(P, Pmax) || (int)blockIdx.x * EV_T >= P) return;
+    const int nt = (P + EV_T - 1) / EV_T;
+    float* wg = ws + (size_t)g * gridDim.x * EV_NW;
+    float a[2] = {0.f, 0.f};
+    for (int r = tid; r < nt; r += 256) {
+        a[0] += wg[(size_t)r * EV_NW + 5];
+        a[1] += wg[(size_t)r * EV_NW + 6];
+    }
+    s_red[0][tid] = a[0];
+    s_red[1][tid] = a[1];
+    block_tree_sum<2>(s_red);
+    const float mean[2] = {s_red[0][0] / (float)(P - 1), s_red[1][0] / (float)(P - 1)};
+    __syncthreads();
+    const float* y = chart + (size_t)g * 9 * Pmax;
+    float tot = 0.f;
+    if (l + 1 < P)
+        for (int c = 0; c < 2; c++) {
+            const float d = ev_vel(y + (size_t)(LL_HIT + c) * Pmax, l, c == 0 ? 512.f : 384.f) - mean[c];
+            tot += d * d;
+        }
+    s_red[0][tid] = tot;
+    block_tree_sum<1>(s_red);
+    if (tid == 0) wg[(size_t)blockIdx.x * EV_NW + 7] = s_red[0][0];
+}
+
+// Block g: the map's partial rows added in tile order, the label error, and the smallest channel variance of z over the map's own
+// latent frames (two passes per channel: the mean, then the squares about it)
+__global__ __launch_bounds__(256) void latent_eval_finalize_kernel(const float* __restrict__ ws, int nt_max, const int* __restrict__ plens,
+                                                                   const float* __restrict__ z, const int* __restrict__ zlens,
+                                                                   const float* __restrict__ pred_labels, const float* __restrict__ true_labels,
+                                                                   float* __restrict__ out, int Pmax, int E, int lmax) {
+    __shared__ float s_red[6][256];
+    const int tid = threadIdx.x, g = blockIdx.x, P = plens[g], zl = zlens[g];
+    float* o = out + (size_t)g * 8;
+    if (!ev_ok(P, Pmax) || zl < 1 || zl > lmax) {
+        if (tid < 8) o[tid] = __builtin_nanf("");
+        return;
+    }
+    const int nt = (P + EV_T - 1) / EV_T;
+    const int col[6] = {0, 1, 2, 3, 7, 4};
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int r = tid; r < nt; r += 256)
+#pragma unroll
+        for (int k = 0; k < 6; k++) acc[k] += ws[((size_t)g * nt_max + r) * EV_NW + col[k]];
+#pragma unroll
+    for (int k = 0; k < 6; k++) s_red[k][tid] = acc[k];
+    block_tree_sum<6>(s_red);
+    if (tid == 0) {
+        for (int k = 0; k < 5; k++) o[k] = s_red[k][0];
+        o[5] = s_red[5][0] / (2.f * (float)P);
+        float q = 0.f;
+        for (int j = 0; j < 5; j++) q += fabsf(pred_labels[g * 5 + j] - true_labels[g * 5 + j]);
+        o[6] = q / 5.f;
+    }
+    float vmin = 0.f;
+    for (int e = 0; e < E; e++) {
+        const float* ze = z + ((size_t)g * E + e) * lmax;
+        __syncthreads();
+        float a = 0.f;
+        for (int t = tid; t < zl; t += 256) a += ze[t];
+        s_red[0][tid] = a;
+        block_tree_sum<1>(s_red);
+        const float mean = s_red[0][0] / (float)zl;
+        __syncthreads();
+        a = 0.f;
+        for (int t = tid; t < zl; t += 256) {
+            const float d = ze[t] - mean;
+            a += d * d;
+        }
+        s_red[0][tid] = a;
+        block_tree_sum<1>(s_red);
+        const float var = s_red[0][0] / (float)(zl - 1);    // unbiased, as torch.var: NaN for a single frame
+        if (e == 0 || var < vmin || var != var) vmin = var;  // the minimum; a NaN stays, as in torch.min
+    }
+    if (tid == 0) o[7] = vmin;
+}
+
 }  // namespace
 
 extern "C" int od_latent_loss_block_frames(void) { return LL_T; }
@@ -1751,6 +2030,47 @@ extern "C" int od_latent_loss(const float* logits, const float* chart, const flo
     OD_LAUNCH(latent_loss_sums_kernel, dim3(nbl, B2), dim3(256), 0, (hipStream_t)stream, logits, chart, ws, L);
     OD_LAUNCH(latent_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, B2 * nbl, pred_labels, true_labels,
               (const unsigned char*)masked, s_reg, loss_ema, (unsigned char*)ema_init, out, coef, B2, L, s_reg_weight, training);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_mmd_imq_pairs(const float* s, const float* prior, float* out, float* ws, long ws_floats, int G, int S, void* stream) {
+    if (G < 1 || S < 1 || S > MMD_DMAX) return OD_ERR_UNSUPPORTED;
+    if (!s || !prior || !out || !ws || ws_floats < (long)G * 6) return OD_ERR_ARG;
+    OD_LAUNCH(mmd_pairs_rows_kernel, dim3(2 * G), dim3(256), 0, (hipStream_t)stream, s, prior, ws, S);
+    OD_LAUNCH(mmd_pairs_finalize_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, ws, out);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_loss_maps(const float* logits, const float* chart, const int* hlens, const float* pred_labels,
+                                   const float* true_labels, const float* s_reg, int s_reg_stride, const float* loss_ema, float* out,
+                                   float* ws, long ws_floats, int G, int Hmax, float s_reg_weight, void* stream) {
+    if (Hmax < 3) return OD_ERR_UNSUPPORTED;
+    if (G < 1 || s_reg_stride < 1 || !logits || !chart || !hlens || !pred_labels || !true_labels || !s_reg || !loss_ema || !out || !ws)
+        return OD_ERR_ARG;
+    const int nbl = (Hmax + LL_T - 1) / LL_T;
+    if (ws_floats < (long)2 * G * nbl * LL_NS) return OD_ERR_ARG;
+    OD_LAUNCH(latent_loss_maps_sums_kernel, dim3(nbl, 2 * G), dim3(256), 0, (hipStream_t)stream, logits, chart, hlens, ws, Hmax);
+    OD_LAUNCH(latent_loss_maps_finalize_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, ws, nbl, hlens, pred_labels, true_labels, s_reg,
+              s_reg_stride, loss_ema, out, Hmax, s_reg_weight);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_latent_eval_maps_ws_floats(int G, int Pmax) { return G * ((Pmax + EV_T - 1) / EV_T) * EV_NW; }
+
+extern "C" int od_latent_eval_maps(const float* chart, const float* pred_chart, const int* plens, const float* z, const int* zlens,
+                                   const float* pred_labels, const float* true_labels, float* out, float* ws, long ws_floats, int G,
+                                   int Pmax, int E, int lmax, void* stream) {
+    if (G < 1 || Pmax < 2 || E < 1 || lmax < 1 || !chart || !pred_chart || !plens || !z || !zlens || !pred_labels || !true_labels || !out || !ws)
+        return OD_ERR_ARG;
+    const int nt = (Pmax + EV_T - 1) / EV_T;
+    if (ws_floats < (long)G * nt * EV_NW) return OD_ERR_ARG;
+    OD_LAUNCH(latent_eval_sums_kernel, dim3(nt, G), dim3(256), 0, (hipStream_t)stream, chart, pred_chart, plens, ws, Pmax);
+    OD_LAUNCH(latent_eval_total_kernel, dim3(nt, G), dim3(256), 0, (hipStream_t)stream, chart, plens, ws, Pmax);
+    OD_LAUNCH(latent_eval_finalize_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, ws, nt, plens, z, zlens, pred_labels, true_labels, out,
+              Pmax, E, lmax);
     OD_CHECK_LAUNCH();
     return 0;
 }

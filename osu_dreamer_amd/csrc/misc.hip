@@ -162,6 +162,27 @@ __global__ __launch_bounds__(256) void feed_gather_quant_kernel(const unsigned c
     }
 }
 
+// ------------------------------------------------------------ resident feed: replicate padding behind a gathered row
+// A wave owns one (n, c) row: frames lens[n] .. plens[n] take the value of frame lens[n] - 1 (read once per lane: a frame the wave never
+// writes).  The tail is shorter than the padding multiple, a few wave-instructions at most.  A row with lens[n] < 1 or plens[n] > Lpad is
+// written as NaN over all of Lpad and nothing of it is loaded; plens[n] <= lens[n] leaves the row as it is.
+__global__ __launch_bounds__(256) void replicate_tail_kernel(float* __restrict__ x, const int* __restrict__ lens, const int* __restrict__ plens,
+                                                             int C, int Lpad, long rows) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
+    if (row >= rows) return;
+    const int n = (int)(row / C);
+    const int len = lens[n], plen = plens[n];
+    float* dst = x + row * Lpad;
+    if (len < 1 || plen > Lpad) {
+        for (int l = lane; l < Lpad; l += 64) dst[l] = __builtin_nanf("");
+        return;
+    }
+    if (plen <= len) return;
+    const float v = dst[len - 1];
+    for (int l = len + lane; l < plen; l += 64) dst[l] = v;
+}
+
 // ------------------------------------------------------------ proj_in: E (<=8) channels -> D
 template <class T>
 __global__ __launch_bounds__(256) void proj_in_kernel(const float* __restrict__ xt, const float* __restrict__ W,
@@ -653,6 +674,15 @@ extern "C" int od_feed_gather_quant(const void* store, long store_bytes, int ele
     else
         OD_LAUNCH(feed_gather_quant_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)store, store_bytes, base,
                   cstride, lens, scale, offset, flip, out, C, c0, Ctot, Lpad, nseg, items);
+    OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_replicate_tail(float* x, const int* lens, const int* plens, int N, int C, int Lpad, void* stream) {
+    if (!x || !lens || !plens || N < 1 || C < 1 || Lpad < 1) return OD_ERR_ARG;
+    const long rows = (long)N * C, blocks = (rows + 3) / 4;
+    if (blocks > 0x7fffffffL) return OD_ERR_UNSUPPORTED;
+    OD_LAUNCH(replicate_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, lens, plens, C, Lpad, rows);
     OD_CHECK_LAUNCH();
     return 0;
 }

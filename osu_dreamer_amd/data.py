@@ -71,6 +71,20 @@ class RaggedLatentBatch(NamedTuple):
     lengths: torch.Tensor  # (N,) int64, on the host
 
 
+class RaggedBeatmapBatch(NamedTuple):
+    """G whole held-out maps of different lengths for the latent model's validation (resident.ResidentBeatmapValFeed), padded as
+    `LatentTrainer.pad_batch` pads each of them alone: map g has lengths[g] frames, then its last frame repeated up to
+    P_g = lengths[g] rounded up to the feed's pad multiple (2 x chunk_size), then zeros up to Pmax = the longest P_g.  The same maps cut in
+    halves come with them, as `latent_train.split_halves` cuts a padded map: row 2g is frames [0, P_g / 2) of map g, row 2g + 1 is frames
+    [P_g / 2, P_g), zeros behind.  What `LatentTrainer.validation_step` accepts beside the batch-1 tuple."""
+    audio: torch.Tensor          # (G, A_DIM, Pmax)
+    chart: torch.Tensor          # (G, X_DIM, Pmax)
+    labels: torch.Tensor         # (G, NUM_LABELS)
+    lengths: torch.Tensor        # (G,) int64, on the host: the maps' own frames, before any padding
+    audio_halves: torch.Tensor   # (2G, A_DIM, Pmax / 2)
+    chart_halves: torch.Tensor   # (2G, X_DIM, Pmax / 2)
+
+
 def collate_ragged(samples: List[LatentBatch], pad_multiple: int = 64) -> RaggedLatentBatch:
     """Whole maps -> one RaggedLatentBatch, zero-padded to the longest map rounded up to `pad_multiple` (few distinct padded lengths: the
     engine keeps one workspace per (N, Lpad))."""

@@ -39,7 +39,7 @@ import torch
 import yaml
 
 from . import _lib, launch
-from .data import LatentDataModule, RaggedLatentBatch
+from .data import LatentDataModule, RaggedBeatmapBatch, RaggedLatentBatch
 from .lr_schedule import LRScheduleArgs
 from .model import BackboneArgs, DiffusionModelArgs
 from .train import DiffusionTrainer
@@ -123,6 +123,8 @@ class Trainer:
     def _to(self, batch, device):
         if isinstance(batch, RaggedLatentBatch):          # the lengths stay on the host: the engine plans with them
             return RaggedLatentBatch(*(t.to(device, non_blocking=True) for t in batch[:4]), batch.lengths)
+        if isinstance(batch, RaggedBeatmapBatch):         # likewise: the validation step plans its varlen calls with them
+            return batch._replace(**{k: t.to(device, non_blocking=True) for k, t in batch._asdict().items() if k != "lengths"})
         return tuple(t.to(device, non_blocking=True) for t in batch)
 
     def save_checkpoint(self, path, module, opt, sched):
@@ -466,16 +468,24 @@ def build_latent_from_config(cfg: Dict[str, Any]):
     return module, trainer
 
 
-def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer"):
+def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer", val_pad_multiple: Optional[int] = None):
     """fit-latent's `data:` block -> its data module.  `data.resident: true` keeps the training set on the device as the integers of its
     files (resident.py: every spec.npy and map read once, batches dequantised, flipped and padded by od_feed_gather_quant), within
-    `data.resident_max_gb` when that is set."""
+    `data.resident_max_gb` when that is set.  `data.resident_val: true` (with data.resident) keeps the held-out maps there too and
+    validates them in ragged groups of at most `data.val_frame_budget` padded frames, each map padded to `val_pad_multiple` (the
+    trainer's 2 x chunk_size)."""
     from .data import BeatmapDataModule
     resident, max_gb = data.pop("resident", False), data.pop("resident_max_gb", None)
+    resident_val, val_budget = data.pop("resident_val", False), data.pop("val_frame_budget", None)
     if not resident:
         if max_gb is not None:
             raise ValueError("data.resident_max_gb bounds the resident store: set data.resident: true, or drop the key")
+        if resident_val or val_budget is not None:
+            raise ValueError("data.resident_val / data.val_frame_budget validate from the resident store: set data.resident: true, or drop "
+                             "the keys")
         return BeatmapDataModule(**data)
+    if val_budget is not None and not resident_val:
+        raise ValueError("data.val_frame_budget sizes the groups of the resident validation: set data.resident_val: true, or drop the key")
     from .resident import ResidentBeatmapDataModule
     if data.get("num_workers") and trainer.rank == 0:
         print(f"data.resident: batches are gathered on the device, data.num_workers={data['num_workers']} is ignored for training")
@@ -485,7 +495,8 @@ def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer"):
         device = torch.device("cpu")         # test-suite only, as in Trainer.fit
     else:
         raise RuntimeError("data.resident needs an MI355X: the store lives in device memory")
-    return ResidentBeatmapDataModule(**data, device=device, resident_max_gb=max_gb)
+    return ResidentBeatmapDataModule(**data, device=device, resident_max_gb=max_gb, resident_val=bool(resident_val),
+                                     val_frame_budget=val_budget, val_pad_multiple=val_pad_multiple)
 
 
 def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
@@ -498,7 +509,7 @@ def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = N
     if cfg.get("seed_everything") not in (None, False):
         seed_everything(cfg["seed_everything"])
     module, trainer = build_latent_from_config(cfg)
-    data = build_beatmap_data(dict(cfg["data"]), trainer)
+    data = build_beatmap_data(dict(cfg["data"]), trainer, val_pad_multiple=2 * module.latent.chunk_size)
     trainer.fit(module, data, ckpt_path=ckpt_path)
     return module, trainer
 

@@ -13,7 +13,9 @@ autograd nodes of this module around it, each a few launches of csrc/latent.hip 
 
 The optimizer is the reference's AdamW with Lightning's global-norm clip (optim.ClippedAdamW); there is no EMA model, parameter arena or
 graph capture here.  The once-per-epoch validation metrics (train.py:176-255) are torch ops on the decoded maps, off the hot path;
-`plot_val` (a TensorBoard figure) is not built.
+`plot_val` (a TensorBoard figure) is not built.  Validation also takes whole maps in ragged groups (data.RaggedBeatmapBatch, from
+`data.resident_val`): the varlen forward calls of LatentModel, then od_mmd_imq_pairs, od_latent_loss_maps and od_latent_eval_maps give every
+map the values of its own per-map step, with one host read per group (`_validation_group`).
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ from typing import Any, Dict, List
 import torch
 
 from . import ops
+from .data import RaggedBeatmapBatch
 from .latent import LatentModel, LatentModelArgs
 from .ldm import pad_to_multiple
 from .lr_schedule import LRScheduleArgs, make_lr_schedule
@@ -218,11 +221,67 @@ class LatentTrainer(_Base):
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx, *args, **pins):
+        if isinstance(batch, RaggedBeatmapBatch):
+            return self._validation_group(batch, **pins)
         batch = self.pad_batch(batch)
         _, log_dict = self(batch, **pins)
         logs = {f"val/{k}": v for k, v in log_dict.items()}
         logs.update(self.eval_metrics(batch))
         self._val.append(logs)
+        return logs
+
+    def _validation_group(self, b: RaggedBeatmapBatch, prior=None) -> List[Dict[str, torch.Tensor]]:
+        """validation_step on G whole maps at once (data.RaggedBeatmapBatch): what the per-map step computes for each of them, by the
+        varlen forward calls and the per-map reductions of csrc/latent.hip, with one device-to-host read for the group.
+
+        Loss part, on the halves (map g = rows 2g, 2g + 1, as split_halves orders them): encode_chart, the MMD of each pair against its
+        rows of one prior draw (2G, S) (`prior=` pins it), the eval-mode perturbation (each half decoded with the other half's style),
+        audio_encoder, decode_logits, the label predictor and od_latent_loss_maps.  Metric part, on the whole maps: encode_chart, decode
+        and od_latent_eval_maps.  `_val` receives one entry per map, in the group's order, and the five epoch sums grow in fp64 in that
+        order."""
+        c, m, dev = self.latent.chunk_size, self.latent, b.chart.device
+        L = [int(x) for x in b.lengths]
+        G, P = len(L), [(x + 2 * c - 1) // (2 * c) * (2 * c) for x in L]
+        if tuple(b.chart.shape) != (G, 9, max(P)) or tuple(b.chart_halves.shape) != (2 * G, 9, max(P) // 2) or min(L) < 2 * c:
+            raise ValueError(f"the group's maps ({L} frames) padded to multiples of 2 x chunk_size = {2 * c} do not give its tensors "
+                             f"{tuple(b.chart.shape)} / {tuple(b.chart_halves.shape)}: the feed's pad multiple must be 2 x chunk_size")
+        hl = [p // 2 for p in P for _ in range(2)]
+        lens = m._dev_i32([hl, P + [0] * G, [p // c for p in P] + [0] * G], dev)
+        hlens, plens, zlens = lens[0], lens[1, :G], lens[2, :G]
+        labels = b.labels.to(F32).contiguous()
+        # ---- the loss of every map's two halves
+        chart_h = b.chart_halves.to(F32).contiguous()
+        z, s = m.encode_chart(chart_h, lengths=hl)
+        prior = torch.randn_like(s) if prior is None else prior.to(dev, F32).contiguous()
+        out = torch.empty(G * (4 + 13 + 8), dtype=F32, device=dev)
+        mmd, loss, ev = out[:4 * G].view(G, 4), out[4 * G:17 * G].view(G, 13), out[17 * G:].view(G, 8)
+        ops.mmd_imq_pairs(s, prior, mmd, torch.empty(6 * G, dtype=F32, device=dev))
+        cfg = (self.s_noise, self.z_noise, self.s_mask_frac, self.z_mask_frac)
+        z_in, s_in, _ = _PerturbFn.apply(z, s, (None,) * 6, cfg, False)
+        skips, _ = m.audio_encoder(b.audio_halves, lengths=hl)
+        logits = m.decode_logits(z_in, s_in, skips=skips, lengths=hl)
+        ws = torch.empty(ops.latent_loss_ws_floats(2 * G, chart_h.shape[-1]), dtype=F32, device=dev)
+        ops.latent_loss_maps(logits, chart_h, hlens, m._label_predictor(s_in), labels.repeat_interleave(2, dim=0).contiguous(), mmd[:, 0],
+                             self.loss_ema, loss, ws, self.s_reg_weight)
+        # ---- the metrics of every whole map
+        chart = b.chart.to(F32).contiguous()
+        z, s = m.encode_chart(chart, lengths=P)
+        pred_chart, pred_labels = m.decode(z, s, audio=b.audio, lengths=P)
+        ws = torch.empty(ops.latent_eval_maps_ws_floats(G, chart.shape[-1]), dtype=F32, device=dev)
+        ops.latent_eval_maps(chart, pred_chart, plens, z, zlens, pred_labels, labels, ev, ws)
+        sums = ev[:, :5].cpu().double()                         # the group's one read; the logged values stay on the device
+        logs = []
+        for g in range(G):
+            d = {f"val/{k}": loss[g, i] for i, k in enumerate(LOG_NAMES)}
+            d.update({"eval/cursor_px_mae": ev[g, 5], "eval/label_mae": ev[g, 6], "eval/z_var_min": ev[g, 7]})
+            tt, pt, pp, res, tot = sums[g].tolist()
+            self._on_tt += tt
+            self._on_pt += pt
+            self._on_pp += pp
+            self._cur_res += res
+            self._cur_tot += tot
+            logs.append(d)
+        self._val.extend(logs)
         return logs
 
     def on_validation_epoch_end(self):

@@ -203,6 +203,17 @@ def feed_gather_quant(store, elem_size, base, cstride, lens, out, c0=0, channels
                                     N, C, c0, Ctot, Lpad, _stream(out))
 
 
+def replicate_tail(x, lens, plens):
+    """x (N, C, Lpad) fp32, in place: frames lens[n] .. plens[n] of every channel of row n take the row's frame lens[n] - 1 (replicate
+    padding; lens, plens: device int32 [N]).  Nothing else is written."""
+    N, C, Lpad = x.shape
+    _f32(x)
+    _lens(lens, N)
+    _lens(plens, N)
+    assert x.device == lens.device == plens.device, "replicate_tail: every tensor on one device"
+    _lib.lib().od_replicate_tail(_p(x), _p(lens), _p(plens), N, C, Lpad, _stream(x))
+
+
 def proj_in(xt, W, bias, x):
     B, E, L = xt.shape
     D = x.shape[1]
@@ -923,3 +934,44 @@ def latent_loss_bwd(logits, chart, pred_labels, true_labels, masked, coef, g, dl
     assert dlogits.shape == logits.shape and tuple(dlabels.shape) == (B2, 5)
     _lib.lib().od_latent_loss_bwd(_p(logits), _p(chart), _p(pred_labels), _p(true_labels), _p(masked), _p(coef), _p(g), _p(dlogits),
                                   _p(dlabels), _p(ds_reg), B2, L, s_reg_weight, _stream(logits))
+
+
+# ---------------------------------------------------------------- latent model, validation over ragged groups (per-map reductions)
+def mmd_imq_pairs(s, prior, out, ws):
+    """out[g] = (MMD^2, zz, pp, zp) of rows 2g, 2g + 1 of s (2G, S) against the same rows of prior: mmd_imq on each pair, no gradient."""
+    N, S = s.shape
+    _f32(s, prior, out, ws)
+    assert N % 2 == 0 and prior.shape == s.shape and tuple(out.shape) == (N // 2, 4) and ws.numel() >= 3 * N
+    _lib.lib().od_mmd_imq_pairs(_p(s), _p(prior), _p(out), _p(ws), ws.numel(), N // 2, S, _stream(s))
+
+
+def latent_loss_maps(logits, chart, hlens, pred_labels, true_labels, s_reg, loss_ema, out, ws, s_reg_weight):
+    """out[g] = the 13 values of latent_loss(training=False) on rows 2g, 2g + 1 of logits / chart (2G, 9, Hmax), each valid for hlens[2g]
+    frames (device int32 [2G]); s_reg: fp32 [G] with any element stride (a column of mmd_imq_pairs' output); loss_ema is read only."""
+    B2, C, Hmax = logits.shape
+    G = B2 // 2
+    _f32(logits, chart, pred_labels, true_labels, loss_ema, out, ws)
+    _lens(hlens, B2)
+    assert C == 9 and B2 % 2 == 0 and chart.shape == logits.shape and tuple(pred_labels.shape) == tuple(true_labels.shape) == (B2, 5)
+    assert s_reg.dtype == torch.float32 and s_reg.dim() == 1 and s_reg.shape[0] == G and (G == 1 or s_reg.stride(0) >= 1)
+    assert loss_ema.numel() == 11 and tuple(out.shape) == (G, 13)
+    _lib.lib().od_latent_loss_maps(_p(logits), _p(chart), _p(hlens), _p(pred_labels), _p(true_labels), _p(s_reg), max(s_reg.stride(0), 1),
+                                   _p(loss_ema), _p(out), _p(ws), ws.numel(), G, Hmax, s_reg_weight, _stream(logits))
+
+
+def latent_eval_maps_ws_floats(G, Pmax) -> int:
+    return _lib.lib().cdll.od_latent_eval_maps_ws_floats(G, Pmax)
+
+
+def latent_eval_maps(chart, pred_chart, plens, z, zlens, pred_labels, true_labels, out, ws):
+    """out[g] = (sum t^2, sum p t, sum p^2 on the onset channel; cursor velocity residual and total sums of squares in pixels; mean |pixel
+    error|; mean |label error|; min over channels of the unbiased variance of z) of map g: chart / pred_chart (G, 9, Pmax) valid for
+    plens[g] frames, z (G, E, lmax) for zlens[g] (device int32 [G] each)."""
+    G, C, Pmax = chart.shape
+    _f32(chart, pred_chart, z, pred_labels, true_labels, out, ws)
+    _lens(plens, G)
+    _lens(zlens, G)
+    assert C == 9 and pred_chart.shape == chart.shape and z.dim() == 3 and z.shape[0] == G
+    assert tuple(pred_labels.shape) == tuple(true_labels.shape) == (G, 5) and tuple(out.shape) == (G, 8)
+    _lib.lib().od_latent_eval_maps(_p(chart), _p(pred_chart), _p(plens), _p(z), _p(zlens), _p(pred_labels), _p(true_labels), _p(out), _p(ws),
+                                   ws.numel(), G, Pmax, z.shape[1], z.shape[2], _stream(chart))

@@ -18,7 +18,8 @@ The latent model's trainer has the same feed over the pre-processed beatmaps (th
 mapset's whole `spec.npy` and the map's npz for every sample of every epoch, widens both to float64 and keeps one window.  Here
 `ResidentBeatmapStore` keeps the files' unsigned integers on the device (spec once per mapset, hit and xy per map), the same `EpochPlanner`
 plans the windows, `ResidentBeatmapFeed` draws their flips, and `od_feed_gather_quant` dequantises, places, flips and pads a batch in three
-launches — bit for bit the host loader's float32 values.
+launches — bit for bit the host loader's float32 values.  With `data.resident_val` the held-out maps live in a second store and are
+validated whole, in ragged groups (`ResidentBeatmapValFeed`): the same gather, then `od_replicate_tail` for the padding `pad_batch` applies.
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ import torch
 
 from . import ops
 from .data import (A_DIM, NUM_LABELS, X_DIM, Batch, BeatmapDataModule, BeatmapDataset, LatentBatch, LatentDataModule, LatentDataset,
-                   RaggedLatentBatch, cut_batches)
+                   RaggedBeatmapBatch, RaggedLatentBatch, cut_batches)
 
 ALL_FIELDS = ("h", "z", "s", "labels")
 STYLE_FIELDS = ("s", "labels")
@@ -410,10 +411,11 @@ class ResidentBeatmapStore:
 
     A 30 000-frame mapset takes 2.2 MB plus 0.33 MB per difficulty: 11 bytes per chart frame against the 324 a float32 batch spends.
     Every size and dtype is read from the files' headers first; `max_bytes`: refuse — before anything is allocated — a store that needs
-    more.  The upload goes through two pinned staging buffers of `staging_bytes` each."""
+    more, counting `reserved_bytes` that another store under the same limit already holds.  The upload goes through two pinned staging
+    buffers of `staging_bytes` each."""
 
     def __init__(self, mapsets: Sequence[Path], device, rank: int = 0, world_size: int = 1, max_bytes: Optional[int] = None,
-                 staging_bytes: int = 32 << 20):
+                 staging_bytes: int = 32 << 20, reserved_bytes: int = 0):
         self.device = torch.device(device)
         self.files = [f for i, f in enumerate(BeatmapDataset(list(mapsets))._files()) if i % world_size == rank]
         if not self.files:
@@ -457,6 +459,10 @@ class ResidentBeatmapStore:
             self.xy_base[i] = nbytes // 2
             nbytes += 2 * 2 * int(self.lengths[i])
         self.nbytes = nbytes + 4 * n * NUM_LABELS
+        if max_bytes is not None and reserved_bytes and self.nbytes + reserved_bytes > max_bytes:
+            raise MemoryError(f"the resident store of the held-out maps needs {self.nbytes} bytes for {n} maps beside the training store's "
+                              f"{int(reserved_bytes)}: together more than the limit of {int(max_bytes)} bytes (data.resident_max_gb = "
+                              f"{max_bytes / 2 ** 30:.2f}): raise the limit, or validate with data.resident_val: false")
         if max_bytes is not None and self.nbytes > max_bytes:
             raise MemoryError(f"the resident store needs {self.nbytes} bytes ({self.nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than the limit of "
                               f"{int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or train with data.resident: false")
@@ -478,6 +484,39 @@ class ResidentBeatmapStore:
 
     def __len__(self):
         return len(self.files)
+
+
+def gather_beatmap_rows(st: ResidentBeatmapStore, pin: bool, maps: np.ndarray, starts: np.ndarray, lens: np.ndarray, Lpad: int,
+                        aux: np.ndarray, flip: bool):
+    """(audio (B, 72, Lpad), chart (B, 9, Lpad), the maps' indices, lens and aux as device int32): row i takes lens[i] frames of map
+    maps[i] from frame starts[i], zeros behind.  Everything the three od_feed_gather_quant launches read per row travels as ONE
+    stream-ordered copy from pinned memory, 11 B 64-bit words: the spectrogram's base and channel stride, the hit and xy bases, the
+    chart's channel stride, the map index (for the labels), xy_rng and xy_min as fp64 (B, 2) each, then the lengths and `aux` as int32.
+    `aux` (B,) is the rows' flip masks when `flip`, else whatever int32 the caller wants on the device beside the lengths."""
+    B = len(maps)
+    # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
+    assert (starts >= 0).all() and (lens >= 1).all() and (lens <= Lpad).all() and (starts + lens <= st.lengths[maps]).all()
+    host = torch.empty(11 * B, dtype=torch.int64, pin_memory=pin)
+    hv = host.numpy()
+    hv[0:B], hv[B:2 * B] = st.spec_base[maps] + starts, st.spec_stride[maps]
+    hv[2 * B:3 * B], hv[3 * B:4 * B] = st.hit_base[maps] + starts, st.xy_base[maps] + starts
+    hv[4 * B:5 * B], hv[5 * B:6 * B] = st.lengths[maps], maps
+    hv[6 * B:8 * B].view(np.float64)[:] = st.xy_rng[maps].reshape(-1)
+    hv[8 * B:10 * B].view(np.float64)[:] = st.xy_min[maps].reshape(-1)
+    i32 = hv[10 * B:].view(np.int32)
+    i32[:B], i32[B:] = lens, aux
+    desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
+    desc.copy_(host, non_blocking=True)
+    rng, lo = desc[6 * B:8 * B].view(torch.float64).view(B, 2), desc[8 * B:10 * B].view(torch.float64).view(B, 2)
+    d32 = desc[10 * B:].view(torch.int32)
+    lens32, aux32 = d32[:B], d32[B:]
+    audio = torch.empty(B, A_DIM, Lpad, dtype=torch.float32, device=st.device)
+    chart = torch.empty(B, X_DIM, Lpad, dtype=torch.float32, device=st.device)
+    ops.feed_gather_quant(st.data, 1, desc[0:B], desc[B:2 * B], lens32, audio)
+    ops.feed_gather_quant(st.data, 1, desc[2 * B:3 * B], desc[4 * B:5 * B], lens32, chart, c0=0, channels=HIT_DIM)
+    ops.feed_gather_quant(st.data, 2, desc[3 * B:4 * B], desc[4 * B:5 * B], lens32, chart, c0=HIT_DIM, channels=2, scale=rng, offset=lo,
+                          flip=aux32 if flip else None)
+    return audio, chart, desc[5 * B:6 * B], lens32, aux32
 
 
 class ResidentBeatmapFeed:
@@ -503,49 +542,103 @@ class ResidentBeatmapFeed:
         return [BeatmapPlanBatch(pb.maps, pb.starts, pb.lens, pb.Lpad, flips[i * B:(i + 1) * B]) for i, pb in enumerate(plan)]
 
     def gather(self, pb: BeatmapPlanBatch) -> Batch:
-        """The device batch of one plan entry.  Everything the three launches read per row travels as ONE stream-ordered copy from pinned
-        memory, 11 B 64-bit words: the spectrogram's base and channel stride, the hit and xy bases, the chart's channel stride, the map
-        index (for the labels), xy_rng and xy_min as fp64 (B, 2) each, then the lengths and the flip masks as int32."""
-        st, B, T = self.store, len(pb.maps), pb.Lpad
-        # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
-        assert (pb.starts >= 0).all() and (pb.lens >= 1).all() and (pb.lens <= T).all() and (pb.starts + pb.lens <= st.lengths[pb.maps]).all()
-        host = torch.empty(11 * B, dtype=torch.int64, pin_memory=self.pin)
-        hv = host.numpy()
-        hv[0:B], hv[B:2 * B] = st.spec_base[pb.maps] + pb.starts, st.spec_stride[pb.maps]
-        hv[2 * B:3 * B], hv[3 * B:4 * B] = st.hit_base[pb.maps] + pb.starts, st.xy_base[pb.maps] + pb.starts
-        hv[4 * B:5 * B], hv[5 * B:6 * B] = st.lengths[pb.maps], pb.maps
-        hv[6 * B:8 * B].view(np.float64)[:] = st.xy_rng[pb.maps].reshape(-1)
-        hv[8 * B:10 * B].view(np.float64)[:] = st.xy_min[pb.maps].reshape(-1)
-        i32 = hv[10 * B:].view(np.int32)
-        i32[:B], i32[B:] = pb.lens, pb.flips
-        desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
-        desc.copy_(host, non_blocking=True)
-        rng, lo = desc[6 * B:8 * B].view(torch.float64).view(B, 2), desc[8 * B:10 * B].view(torch.float64).view(B, 2)
-        d32 = desc[10 * B:].view(torch.int32)
-        lens32, flips = d32[:B], d32[B:]
-        audio = torch.empty(B, A_DIM, T, dtype=torch.float32, device=st.device)
-        chart = torch.empty(B, X_DIM, T, dtype=torch.float32, device=st.device)
-        ops.feed_gather_quant(st.data, 1, desc[0:B], desc[B:2 * B], lens32, audio)
-        ops.feed_gather_quant(st.data, 1, desc[2 * B:3 * B], desc[4 * B:5 * B], lens32, chart, c0=0, channels=HIT_DIM)
-        ops.feed_gather_quant(st.data, 2, desc[3 * B:4 * B], desc[4 * B:5 * B], lens32, chart, c0=HIT_DIM, channels=2, scale=rng, offset=lo, flip=flips)
-        return Batch(audio, chart, st.labels.index_select(0, desc[5 * B:6 * B]))
+        """The device batch of one plan entry (gather_beatmap_rows with the windows' flip masks)."""
+        audio, chart, idx, _, _ = gather_beatmap_rows(self.store, self.pin, pb.maps, pb.starts, pb.lens, pb.Lpad, pb.flips, flip=True)
+        return Batch(audio, chart, self.store.labels.index_select(0, idx))
 
     def __iter__(self) -> Iterator[Batch]:
         for pb in self.plan_epoch():
             yield self.gather(pb)
 
 
+class ResidentBeatmapValFeed:
+    """Re-iterable over one validation epoch of the held-out maps in `store`, whole maps in ragged groups (`data.RaggedBeatmapBatch`).
+
+    The plan is made once, from the store's lengths: a map of L frames pads to P = L rounded up to `pad_multiple` (the trainer's
+    2 x chunk_size, what `LatentTrainer.pad_batch` pads a map to), and the maps are packed longest first (encode_latents.pack) into groups
+    whose count x longest P stays within `frame_budget`; a map longer than the budget goes alone.  A group is gathered twice — whole maps
+    (G, 72 | 9, Pmax), and their halves (2G, 72 | 9, Pmax / 2): row 2g frames [0, P_g / 2) of map g, row 2g + 1 frames [P_g / 2, L_g) —
+    each time by three od_feed_gather_quant launches behind one descriptor copy, and od_replicate_tail then repeats every row's last frame
+    up to its padded length.  The values are bit for bit those of read_spec / read_beatmap, .float() and pad_batch; there are no flips.
+
+    A map shorter than `pad_multiple` frames pads to P = pad_multiple with a second half that may hold no frame of its own (nothing to
+    replicate from inside that row), so such maps are not grouped: they follow the groups one by one as unpadded batch-1 `data.Batch`es,
+    which `LatentTrainer.validation_step` pads and evaluates as it always has.  A spectrogram longer than its chart is cut to the chart's
+    frames."""
+
+    def __init__(self, store: ResidentBeatmapStore, pad_multiple: int, frame_budget: Optional[int] = None):
+        from .encode_latents import DEFAULT_FRAME_BUDGET, pack
+        if pad_multiple < 2 or pad_multiple % 2:
+            raise ValueError(f"pad_multiple must be an even number of frames (2 x chunk_size), got {pad_multiple}")
+        self.store, self.pad_multiple = store, int(pad_multiple)
+        self.frame_budget = int(DEFAULT_FRAME_BUDGET if frame_budget is None else frame_budget)
+        if self.frame_budget < 1:
+            raise ValueError(f"data.val_frame_budget must be at least 1 frame, got {frame_budget}")
+        self.plens = (store.lengths + self.pad_multiple - 1) // self.pad_multiple * self.pad_multiple
+        whole = np.nonzero(store.lengths >= self.pad_multiple)[0]
+        self.groups: List[np.ndarray] = [whole[g] for g in pack(self.plens[whole].tolist(), self.frame_budget)]
+        self.short: np.ndarray = np.nonzero(store.lengths < self.pad_multiple)[0]
+        self.pin = store.device.type == "cuda"
+
+    def __len__(self):
+        return len(self.groups) + len(self.short)
+
+    def padded_share(self) -> List[float]:
+        """Per group, the share of its G x Pmax frames that belong to no map (replicated tails and zeros)."""
+        return [1.0 - float(self.store.lengths[g].sum()) / (len(g) * int(self.plens[g].max())) for g in self.groups]
+
+    def _gather(self, maps: np.ndarray, starts: np.ndarray, lens: np.ndarray, plens: np.ndarray, Lpad: int):
+        """(audio (B, 72, Lpad), chart (B, 9, Lpad), the maps' indices on the device): row i takes lens[i] frames of map maps[i] from
+        starts[i], its last frame repeated up to plens[i], zeros behind; plens rides in the descriptor copy in the place of the flip masks."""
+        assert (lens <= plens).all() and (plens <= Lpad).all()
+        audio, chart, idx, lens32, plens32 = gather_beatmap_rows(self.store, self.pin, maps, starts, lens, Lpad, plens, flip=False)
+        if (plens > lens).any():
+            ops.replicate_tail(audio, lens32, plens32)
+            ops.replicate_tail(chart, lens32, plens32)
+        return audio, chart, idx
+
+    def gather(self, maps: np.ndarray) -> RaggedBeatmapBatch:
+        """The device batch of one group: its whole maps and their halves."""
+        st = self.store
+        L, P = st.lengths[maps], self.plens[maps]
+        H = P // 2                                            # L > P - pad_multiple >= P / 2: both halves hold frames of the map
+        audio, chart, idx = self._gather(maps, np.zeros_like(L), L, P, int(P.max()))
+        two = np.repeat(maps, 2)
+        starts, lens = np.stack([np.zeros_like(H), H], 1).reshape(-1), np.stack([H, L - H], 1).reshape(-1)
+        audio_h, chart_h, _ = self._gather(two, starts, lens, np.repeat(H, 2), int(H.max()))
+        return RaggedBeatmapBatch(audio, chart, st.labels.index_select(0, idx), torch.from_numpy(L.astype(np.int64)), audio_h, chart_h)
+
+    def gather_one(self, m: int) -> Batch:
+        """Map m alone and unpadded, as the host loader's batch-1 tuple."""
+        maps = np.asarray([m], dtype=np.int64)
+        L = self.store.lengths[maps]
+        audio, chart, idx = self._gather(maps, np.zeros_like(L), L, L, int(L[0]))
+        return Batch(audio, chart, self.store.labels.index_select(0, idx))
+
+    def __iter__(self) -> Iterator:
+        for g in self.groups:
+            yield self.gather(g)
+        for m in self.short.tolist():
+            yield self.gather_one(m)
+
+
 class ResidentBeatmapDataModule:
     """`BeatmapDataModule` with the training set resident on `device`: the same constructor keys (the YAML `data:` block of fit-latent)
-    plus `device` and `resident_max_gb`.  The host module holds out the validation mapsets and keeps the validation loader (validation
-    reads whole maps once per check), which is all `num_workers` still serves; `shuffle_buffer_size` serves nothing: an epoch is a full
-    permutation of its windows."""
+    plus `device`, `resident_max_gb`, and `resident_val` with `val_frame_budget` and `val_pad_multiple`.  The host module holds out the
+    validation mapsets and, unless `resident_val`, keeps the validation loader (whole maps read once per check), which is all
+    `num_workers` still serves; `shuffle_buffer_size` serves nothing: an epoch is a full permutation of its windows.  With `resident_val`
+    the held-out maps go, on first use, into a second store under the same `resident_max_gb`, and validation reads ragged groups from it
+    (ResidentBeatmapValFeed); `val_pad_multiple` is the trainer's 2 x chunk_size (fit-latent passes it)."""
 
     def __init__(self, batch_size: int, seq_len: int, num_workers: int = 0, max_val_count: int = 512, max_val_frac: float = .3,
                  data_path: str = "./data", shuffle_buffer_size: int = 1, max_per_map: int = -1, rank: int = 0, world_size: int = 1,
-                 device=None, resident_max_gb: Optional[float] = None):
+                 device=None, resident_max_gb: Optional[float] = None, resident_val: bool = False, val_frame_budget: Optional[int] = None,
+                 val_pad_multiple: Optional[int] = None):
         if seq_len is None:
             raise ValueError("data.resident trains fit-latent on fixed windows: data.seq_len must be an integer")
+        if resident_val and val_pad_multiple is None:
+            raise ValueError("data.resident_val pads every held-out map as the trainer does: val_pad_multiple (2 x the model's chunk_size) "
+                             "is needed")
         self.host = BeatmapDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
                                       rank, world_size)
         if device is None:
@@ -555,9 +648,18 @@ class ResidentBeatmapDataModule:
         self.store = ResidentBeatmapStore(self.host.train_set.mapsets, self.device, rank, world_size, max_bytes)
         self.planner = EpochPlanner(self.store.lengths, batch_size, int(seq_len), max_per_map)
         self.feed = ResidentBeatmapFeed(self.store, self.planner, rank)
+        self.resident_val, self._max_bytes = bool(resident_val), max_bytes
+        self._val_args = (val_pad_multiple, val_frame_budget)
+        self.val_feed: Optional[ResidentBeatmapValFeed] = None
 
     def train_dataloader(self) -> ResidentBeatmapFeed:
         return self.feed
 
     def val_dataloader(self):
-        return self.host.val_dataloader()
+        if not self.resident_val:
+            return self.host.val_dataloader()
+        if self.val_feed is None:
+            # refused, before anything is allocated, if it does not fit under resident_max_gb beside the training store
+            val_store = ResidentBeatmapStore(self.host.val_set.mapsets, self.device, max_bytes=self._max_bytes, reserved_bytes=self.store.nbytes)
+            self.val_feed = ResidentBeatmapValFeed(val_store, *self._val_args)
+        return self.val_feed
