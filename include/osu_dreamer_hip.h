@@ -108,7 +108,9 @@ int od_cl_to_frames(int dtype, const float* src, void* dst, int ldd, int B, int 
  *   out[n][c][l] = l < lens[n] ? store[base[n] + c * cstride[n] + l] : 0
  * The zeros are selected, not multiplied (out may hold anything on entry), and nothing at or past lens[n] of a row is loaded, so a row may
  * end the store.  base[n] is arbitrary: rows whose source and destination are both 16-byte aligned move 16 bytes per lane, the others a
- * dword.  A row whose descriptor does not lie inside the store comes back as NaN.  OD_ERR_ARG: a null pointer or N, C, Lpad, store_elems < 1.
+ * dword.  A row whose descriptor does not lie inside the store — lens[n] outside 1..Lpad, base[n] or cstride[n] outside 0..store_elems (so
+ * no product of theirs can wrap), or any channel's base[n] + c * cstride[n] outside 0..store_elems - lens[n] — comes back as NaN (the
+ * whole row, or that channel) and nothing is loaded for it: od_feed_gather_quant's rule.  OD_ERR_ARG: a null pointer or N, C, Lpad, store_elems < 1.
  * replaces: data/modules/latent.py:74-80 with the window slices of LatentDataset.make_samples, and collate_ragged here — the
  * host loader's load, crop, zero-padded collate and host-to-device copy of a batch. */
 int od_feed_gather(const float* store, long store_elems, const long* base, const long* cstride, const int* lens, float* out,

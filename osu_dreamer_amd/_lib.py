@@ -101,6 +101,20 @@ def loaded_path() -> Optional[str]:
     return _lib.path if _lib is not None else None
 
 
+_NO_GPU = {"training": "osu_dreamer_amd has no CPU path", "data.resident": "the store lives in device memory"}
+
+
+def training_device(local_rank: Optional[int], what: str):
+    """The torch device `what` ("training" or "data.resident") runs on: GPU `local_rank` (None: the current one), else — test-suite only —
+    the CPU when the kernels are bound to the SIMT emulator build, else an error."""
+    import torch
+    if torch.cuda.is_available():
+        return torch.device("cuda", torch.cuda.current_device() if local_rank is None else local_rank)
+    if loaded_path() not in (None, DEFAULT_SO):
+        return torch.device("cpu")
+    raise RuntimeError(f"{what} needs an MI355X: {_NO_GPU[what]}")
+
+
 def source_sha() -> str:
     """Hash of the kernel sources the loaded library was built from (od_build_source_sha)."""
     return lib().cdll.od_build_source_sha().decode()

@@ -22,34 +22,51 @@ __global__ __launch_bounds__(256) void cl_to_frames_kernel(const float* __restri
     }
 }
 
-// ------------------------------------------------------------ resident feed: flat fp32 store -> padded (N, C, Lpad) batch
+// ------------------------------------------------------------ resident feed: the row a wave gathers
 // A wave owns FG_SEG frames of one (n, c) row, so the row's descriptor (base, channel stride, valid length) and the choice of path are
-// wave-uniform.  A pure copy, bound by bandwidth: 16 bytes per lane when the row's source and destination are both 16-byte aligned
-// (1 KiB per wave-instruction), else one dword per lane with four independent loads in flight (256 contiguous bytes per wave-instruction
-// on both sides: the shape that still streams at the memory's rate; the destination alone being aligned does not help, a 16-byte store fed
-// by four strided dword loads touches every line four times).  Frames >= len are SELECTED as zero, never loaded: the quad that straddles
-// len is peeled element by element, so a row that ends the store is not read past.  A row whose descriptor does not lie inside the store
-// (or whose len is outside 1..Lpad) is written as NaN and nothing of it is loaded.
+// wave-uniform.  The descriptor is checked against the store before anything is formed from it: len in 1..Lpad and 0 <= b0, cs <=
+// store_elems first, so that c * cs cannot overflow for a descriptor that passes (C < 2^31, store_elems < 2^62 / C in any real store), then
+// 0 <= s0 <= store_elems - len.  Out: the row (n, c), the wave's frames [l0, l1) of Lpad, s0 (64-bit: a real store exceeds 2^31 elements),
+// the valid length and what the frames behind it take — len and 0, or 0 and NaN for a row that fails: it is written as NaN and nothing of it
+// is loaded.  False: the wave lies behind the last item.
 constexpr int FG_SEG = 1024;
+__device__ __forceinline__ bool feed_row(long store_elems, const long* __restrict__ base, const long* __restrict__ cstride,
+                                         const int* __restrict__ lens, int C, int Lpad, int nseg, long items, int& n, int& c, int& l0, int& l1,
+                                         long& s0, int& len, float& fill) {
+    const long w = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
+    if (w >= items) return false;
+    const long row = w / nseg;
+    const int seg = (int)(w - row * nseg);
+    n = (int)(row / C);
+    c = (int)(row - (long)n * C);
+    const long b0 = base[n], cs = cstride[n];
+    len = lens[n];
+    const bool sane = len >= 1 && len <= Lpad && b0 >= 0 && cs >= 0 && b0 <= store_elems && cs <= store_elems;
+    s0 = sane ? b0 + (long)c * cs : 0;
+    const bool ok = sane && s0 >= 0 && s0 <= store_elems - len;
+    fill = ok ? 0.f : __builtin_nanf("");
+    if (!ok) len = 0;
+    l0 = seg * FG_SEG;
+    l1 = l0 + FG_SEG < Lpad ? l0 + FG_SEG : Lpad;
+    return true;
+}
+
+// ------------------------------------------------------------ resident feed: flat fp32 store -> padded (N, C, Lpad) batch
+// A pure copy of the row feed_row names, bound by bandwidth: 16 bytes per lane when the row's source and destination are both 16-byte
+// aligned (1 KiB per wave-instruction), else one dword per lane with four independent loads in flight (256 contiguous bytes per
+// wave-instruction on both sides: the shape that still streams at the memory's rate; the destination alone being aligned does not help, a
+// 16-byte store fed by four strided dword loads touches every line four times).  Frames >= len are SELECTED as zero, never loaded: the quad
+// that straddles len is peeled element by element, so a row that ends the store is not read past.
 __global__ __launch_bounds__(256) void feed_gather_kernel(const float* __restrict__ store, long store_elems, const long* __restrict__ base,
                                                           const long* __restrict__ cstride, const int* __restrict__ lens,
                                                           float* __restrict__ out, int C, int Lpad, int nseg, long items) {
     const int lane = threadIdx.x & 63;
-    const long w = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
-    if (w >= items) return;
-    const long row = w / nseg;
-    const int seg = (int)(w - row * nseg);
-    const int n = (int)(row / C), c = (int)(row - (long)n * C);
-    const long b0 = base[n], cs = cstride[n];
-    int len = lens[n];
-    const long s0 = b0 + (long)c * cs;                      // 64-bit: a real store exceeds 2^31 elements
-    const bool ok = len >= 1 && len <= Lpad && b0 >= 0 && cs >= 0 && s0 >= 0 && s0 <= store_elems - len;
-    const float fill = ok ? 0.f : __builtin_nanf("");
-    if (!ok) len = 0;
+    int n, c, l0, l1, len;
+    long s0;
+    float fill;
+    if (!feed_row(store_elems, base, cstride, lens, C, Lpad, nseg, items, n, c, l0, l1, s0, len, fill)) return;
     const float* src = store + s0;                          // dereferenced under l < len only
-    float* dst = out + row * Lpad;
-    const int l0 = seg * FG_SEG;
-    const int l1 = l0 + FG_SEG < Lpad ? l0 + FG_SEG : Lpad;
+    float* dst = out + ((long)n * C + c) * Lpad;
     if ((Lpad & 3) == 0 && ((((size_t)src) | ((size_t)dst)) & 15) == 0) {
         for (int l = l0 + lane * 4; l < l1; l += 256) {     // Lpad % 4 == 0: a quad that starts below l1 ends at or below it
             f32x4 v;
@@ -73,7 +90,7 @@ __global__ __launch_bounds__(256) void feed_gather_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------ resident feed: quantised store -> padded fp32 (N, Ctot, Lpad) batch
-// The same wave-per-segment shape as feed_gather_kernel, reading unsigned integers of ES bytes and writing fp32: four bytes stored for
+// The same row (feed_row) as feed_gather_kernel, reading unsigned integers of ES bytes and writing fp32: four bytes stored for
 // every byte read, so the stores set the pace.  A lane owns four consecutive frames and stores them as one 16-byte access when the row's
 // destination is 16-byte aligned.  Its four codes come from ALIGNED dwords of the store, shifted into place by the row's (wave-uniform)
 // byte residue: a window starts at any frame, so its source is dword-aligned one time in four, and four byte loads per 16-byte store would
@@ -102,28 +119,16 @@ __global__ __launch_bounds__(256) void feed_gather_quant_kernel(const unsigned c
                                                                 int Lpad, int nseg, long items) {
     typedef typename std::conditional<ES == 1, unsigned char, unsigned short>::type Q;
     const int lane = threadIdx.x & 63;
-    const long w = (long)blockIdx.x * 4 + od_uniform((int)(threadIdx.x >> 6));
-    if (w >= items) return;
-    const long row = w / nseg;
-    const int seg = (int)(w - row * nseg);
-    const int n = (int)(row / C), c = (int)(row - (long)n * C);
-    const long store_elems = store_bytes / ES;
-    const long b0 = base[n], cs = cstride[n];
-    int len = lens[n];
-    // b0, cs <= store_elems first: c * cs cannot overflow for a descriptor that passes (C < 2^31, store_elems < 2^62 / C in any real store)
-    const bool sane = len >= 1 && len <= Lpad && b0 >= 0 && cs >= 0 && b0 <= store_elems && cs <= store_elems;
-    const long s0 = sane ? b0 + (long)c * cs : 0;
-    const bool ok = sane && s0 >= 0 && s0 <= store_elems - len;
-    const float fill = ok ? 0.f : __builtin_nanf("");
-    if (!ok) len = 0;
+    int n, c, l0, l1, len;
+    long s0;
+    float fill;
+    if (!feed_row(store_bytes / ES, base, cstride, lens, C, Lpad, nseg, items, n, c, l0, l1, s0, len, fill)) return;
     const double qmax = ES == 1 ? 255.0 : 65535.0;
     const bool affine = scale != nullptr;
     const double sc = affine ? scale[(long)n * C + c] : 1.0, of = affine ? offset[(long)n * C + c] : 0.0;
     const bool flip = flipmask != nullptr && ((flipmask[n] >> c) & 1);
     const Q* src = (const Q*)store + s0;                    // dereferenced under l < len only
     float* dst = out + ((long)n * Ctot + c0 + c) * Lpad;
-    const int l0 = seg * FG_SEG;
-    const int l1 = l0 + FG_SEG < Lpad ? l0 + FG_SEG : Lpad;
     if ((Lpad & 3) == 0 && (((size_t)dst) & 15) == 0 && (((size_t)store) & 3) == 0) {
         const unsigned* s32 = (const unsigned*)store;
         const long sbyte = s0 * ES;

@@ -39,7 +39,7 @@ import torch
 import yaml
 
 from . import _lib, launch
-from .data import LatentDataModule, RaggedBeatmapBatch, RaggedLatentBatch
+from .data import LatentDataModule
 from .lr_schedule import LRScheduleArgs
 from .model import BackboneArgs, DiffusionModelArgs
 from .train import DiffusionTrainer
@@ -121,10 +121,8 @@ class Trainer:
         return torch.autocast(device.type, enabled=False)
 
     def _to(self, batch, device):
-        if isinstance(batch, RaggedLatentBatch):          # the lengths stay on the host: the engine plans with them
-            return RaggedLatentBatch(*(t.to(device, non_blocking=True) for t in batch[:4]), batch.lengths)
-        if isinstance(batch, RaggedBeatmapBatch):         # likewise: the validation step plans its varlen calls with them
-            return batch._replace(**{k: t.to(device, non_blocking=True) for k, t in batch._asdict().items() if k != "lengths"})
+        if hasattr(batch, "lengths"):      # a ragged batch: the lengths stay on the host, the engine plans its varlen calls with them
+            return type(batch)(*(t if k == "lengths" else t.to(device, non_blocking=True) for k, t in zip(batch._fields, batch)))
         return tuple(t.to(device, non_blocking=True) for t in batch)
 
     def save_checkpoint(self, path, module, opt, sched):
@@ -145,37 +143,33 @@ class Trainer:
         n = 0
         was_training = module.training
         module.eval()                                 # Lightning runs validation in eval mode (Dropout1d off)
-        if getattr(module, "validates_by_epoch", False):
-            # the module gathers its batches and logs at the end of the validation epoch (StyleTrainer, style/train.py:111-150)
+        # by_epoch: the module gathers its batches and logs at the end of the validation epoch (StyleTrainer, style/train.py:111-150), so
+        # autocast covers that end and not the steps; otherwise every step runs under autocast and returns logs to average
+        by_epoch = getattr(module, "validates_by_epoch", False)
+        if by_epoch:
             module.on_validation_epoch_start()
-            for i, batch in enumerate(datamodule.val_dataloader()):
-                if self.limit_val_batches is not None and i >= self.limit_val_batches:
-                    break
-                module.validation_step(self._to(batch, device), i)
-            with self._autocast(device):
-                logs = module.on_validation_epoch_end()
-            module.train(was_training)
-            return {k: float(v) for k, v in logs.items()}
         for i, batch in enumerate(datamodule.val_dataloader()):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
-            with self._autocast(device):
+            with contextlib.nullcontext() if by_epoch else self._autocast(device):
                 logs = module.validation_step(self._to(batch, device), i)
-            for k, v in logs.items():
-                sums[k] = sums.get(k, 0.0) + float(v)
-            n += 1
+            if not by_epoch:
+                for k, v in logs.items():
+                    sums[k] = sums.get(k, 0.0) + float(v)
+                n += 1
+        if by_epoch:
+            with self._autocast(device):
+                out = {k: float(v) for k, v in module.on_validation_epoch_end().items()}
+        else:
+            out = {f"val/{k}": v / max(n, 1) for k, v in sums.items()}
         module.train(was_training)
-        return {f"val/{k}": v / max(n, 1) for k, v in sums.items()}
+        return out
 
     def fit(self, module: DiffusionTrainer, datamodule, ckpt_path: Optional[str] = None):
-        if torch.cuda.is_available():
-            torch.cuda.set_device(self.local_rank)
-            device = torch.device("cuda", self.local_rank)
-        elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
-            device = torch.device("cpu")     # test-suite only: kernels bound to the SIMT emulator build
-        else:
-            raise RuntimeError("training needs an MI355X: osu_dreamer_amd has no CPU path")
-        reducer, own_group = None, False
+        device = _lib.training_device(self.local_rank, "training")
+        if device.type == "cuda":
+            torch.cuda.set_device(device)
+        own_group = False
         if self.world > 1:
             import torch.distributed as dist
             if not dist.is_initialized():
@@ -187,28 +181,29 @@ class Trainer:
         except BaseException:
             # failure (possibly a dead peer): nothing that waits for the device or for other ranks — abort the RCCL communicator and let
             # the exception end the process; the launcher (torchrun agent) then stops the remaining ranks and returns non-zero
-            net = getattr(module, "diffusion", None)
-            reducer = getattr(net, "_reducer", None)
-            if reducer is not None:
-                try:
-                    reducer.close(abort=True)
-                except Exception:
-                    pass
-                net._reducer = None
+            self._close_reducer(module, abort=True)
             raise
         # orderly teardown: drain the device, destroy the communicator the C ABI created, then the process group — but only a group this
         # call initialised (left to interpreter exit the order is arbitrary and RCCL can hang or abort there)
         if device.type == "cuda":
             torch.cuda.synchronize()
-        net = getattr(module, "diffusion", None)
-        reducer = getattr(net, "_reducer", None)
-        if reducer is not None:
-            reducer.close()
-            net._reducer = None
+        self._close_reducer(module, abort=False)
         if own_group:
             import torch.distributed as dist
             dist.destroy_process_group()
         return out
+
+    @staticmethod
+    def _close_reducer(module, abort: bool):
+        net = getattr(module, "diffusion", None)
+        reducer = getattr(net, "_reducer", None)
+        if reducer is not None:
+            try:
+                reducer.close(abort=abort)
+            except Exception:
+                if not abort:         # an abort is already on the way out with the failure that caused it
+                    raise
+            net._reducer = None
 
     def train_group(self, module, opt, sched, batches, device, batch_idx: int = 0):
         """One optimizer step on `batches` (already on `device`): the group of micro-batches of gradient accumulation, or the one batch of a
@@ -342,28 +337,36 @@ class Trainer:
         return score + min_delta < best if self.monitor_mode == "min" else score - min_delta > best
 
 
+def trainer_kwargs(cfg: Dict[str, Any], command: str, **defaults) -> Dict[str, Any]:
+    """The `trainer:` block as Trainer's keywords: without the keys only Lightning reads, with the command's `defaults`.  fit-style and
+    fit-latent train on one device and cannot accumulate: either key set otherwise is an error, not a key that is dropped."""
+    t = dict(cfg.get("trainer", {}))
+    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
+        t.pop(k, None)
+    if t.get("accumulate_grad_batches") is None:
+        t.pop("accumulate_grad_batches", None)
+    if command == "fit-denoiser":
+        return t
+    k = t.pop("accumulate_grad_batches", 1)
+    if k != 1:
+        raise RuntimeError(f"trainer.accumulate_grad_batches={k} is not implemented for {command}: the model's backward hands out views of a "
+                           "per-step gradient buffer, so a second micro-batch would overwrite the first one's gradients instead of adding to "
+                           "them.  Set trainer.accumulate_grad_batches: 1 (or drop the key); fit-denoiser accumulates")
+    for key, v in defaults.items():
+        t.setdefault(key, v)
+    if launch.parse_devices(t.get("devices", 1)) > 1:
+        raise RuntimeError(f"{command} trains on one device (trainer.devices={t['devices']}): the reference trains the {command[4:]} model on "
+                           "one GPU, and the gradient exchange (GradBucketReducer) is tied to the denoiser's arena")
+    return t
+
+
 def build_from_config(cfg: Dict[str, Any]):
     m = dict(cfg["model"])
     da = dict(m["diffusion_args"])
     da["backbone_args"] = BackboneArgs(**da["backbone_args"])
     m["diffusion_args"] = DiffusionModelArgs(**da)
     m["schedule_args"] = LRScheduleArgs(**m["schedule_args"])
-    module = DiffusionTrainer(**m)
-    t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
-        t.pop(k, None)
-    if t.get("accumulate_grad_batches") is None:
-        t.pop("accumulate_grad_batches", None)
-    return module, Trainer(**t)
-
-
-def refuse_accumulation(t: Dict[str, Any], command: str):
-    """`trainer.accumulate_grad_batches` other than 1 for a trainer that cannot accumulate: an error, not a key that is dropped."""
-    k = t.pop("accumulate_grad_batches", None)
-    if k not in (None, 1):
-        raise RuntimeError(f"trainer.accumulate_grad_batches={k} is not implemented for {command}: the model's backward hands out views of a "
-                           "per-step gradient buffer, so a second micro-batch would overwrite the first one's gradients instead of adding to "
-                           "them.  Set trainer.accumulate_grad_batches: 1 (or drop the key); fit-denoiser accumulates")
+    return DiffusionTrainer(**m), Trainer(**trainer_kwargs(cfg, "fit-denoiser"))
 
 
 def refuse_ragged_data_parallel(cfg: Dict[str, Any], devices: int):
@@ -375,35 +378,44 @@ def refuse_ragged_data_parallel(cfg: Dict[str, Any], devices: int):
                            "data.seq_len) on several devices")
 
 
-def build_latent_data(data: Dict[str, Any], trainer: "Trainer", style_only: bool = False, **shard):
-    """The `data:` block -> its data module.  `data.resident: true` keeps the training set on the device (resident.py: every file read once,
-    batches gathered by od_feed_gather), within `data.resident_max_gb` when that is set; fit-style's store holds the style fields only."""
+def pop_resident(data: Dict[str, Any], trainer: "Trainer") -> Optional[Dict[str, Any]]:
+    """Takes `resident` and `resident_max_gb` out of the `data:` block.  None: the host loader; else the resident data module's `device`
+    and `resident_max_gb` keywords."""
     resident, max_gb = data.pop("resident", False), data.pop("resident_max_gb", None)
     if not resident:
         if max_gb is not None:
             raise ValueError("data.resident_max_gb bounds the resident store: set data.resident: true, or drop the key")
-        return LatentDataModule(**data, **shard)
-    from .resident import STYLE_FIELDS, ALL_FIELDS, ResidentLatentDataModule
+        return None
     if data.get("num_workers") and trainer.rank == 0:
         print(f"data.resident: batches are gathered on the device, data.num_workers={data['num_workers']} is ignored for training")
-    if torch.cuda.is_available():
-        device = torch.device("cuda", trainer.local_rank)
-    elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
-        device = torch.device("cpu")         # test-suite only, as in Trainer.fit
-    else:
-        raise RuntimeError("data.resident needs an MI355X: the store lives in device memory")
-    return ResidentLatentDataModule(**data, **shard, device=device, fields=STYLE_FIELDS if style_only else ALL_FIELDS, resident_max_gb=max_gb)
+    return dict(device=_lib.training_device(trainer.local_rank, "data.resident"), resident_max_gb=max_gb)
 
 
-def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
-    """begin a training run for the diffusion model (reference: scripts/fit_denoiser.py:17-32)."""
+def build_latent_data(data: Dict[str, Any], trainer: "Trainer", style_only: bool = False, **shard):
+    """The `data:` block -> its data module.  `data.resident: true` keeps the training set on the device (resident.py: every file read once,
+    batches gathered by od_feed_gather), within `data.resident_max_gb` when that is set; fit-style's store holds the style fields only."""
+    resident = pop_resident(data, trainer)
+    if resident is None:
+        return LatentDataModule(**data, **shard)
+    from .resident import STYLE_FIELDS, ALL_FIELDS, ResidentLatentDataModule
+    return ResidentLatentDataModule(**data, **shard, **resident, fields=STYLE_FIELDS if style_only else ALL_FIELDS)
+
+
+def load_config(config: str, overrides: Dict[str, Any]) -> Dict[str, Any]:
+    """The YAML with the `section__key=value` overrides applied (e.g. data__data_path="..."), and everything seeded as it asks."""
     with open(config) as f:
         cfg = yaml.safe_load(f)
-    for k, v in overrides.items():          # e.g. data__data_path="..."
+    for k, v in overrides.items():
         sec, key = k.split("__")
         cfg.setdefault(sec, {})[key] = v
     if cfg.get("seed_everything") not in (None, False):
         seed_everything(cfg["seed_everything"])
+    return cfg
+
+
+def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
+    """begin a training run for the diffusion model (reference: scripts/fit_denoiser.py:17-32)."""
+    cfg = load_config(config, overrides)
     devices = launch.parse_devices(cfg.get("trainer", {}).get("devices", 1))
     refuse_ragged_data_parallel(cfg, devices)
     if devices > 1 and launch.world_from_env() is None:
@@ -421,27 +433,12 @@ def build_style_from_config(cfg: Dict[str, Any]):
     from .style_train import StyleTrainer
     m = dict(cfg["model"])
     m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))       # models/style/model.yml leaves the schedule at its defaults
-    t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
-        t.pop(k, None)
-    refuse_accumulation(t, "fit-style")
-    t.setdefault("monitor", "val/energy_dist")
-    t.setdefault("default_root_dir", "runs/style")
-    if launch.parse_devices(t.get("devices", 1)) > 1:
-        raise RuntimeError(f"fit-style trains on one device (trainer.devices={t['devices']}): the reference trains the style model on one "
-                           "GPU, and the gradient exchange (GradBucketReducer) is tied to the denoiser's arena")
-    return StyleTrainer(**m), Trainer(**t)
+    return StyleTrainer(**m), Trainer(**trainer_kwargs(cfg, "fit-style", monitor="val/energy_dist", default_root_dir="runs/style"))
 
 
 def fit_style(config: str = DEFAULT_STYLE_CONFIG, ckpt_path: Optional[str] = None, **overrides):
     """begin a training run for the style model (reference: scripts/fit_style.py:17-32)."""
-    with open(config) as f:
-        cfg = yaml.safe_load(f)
-    for k, v in overrides.items():
-        sec, key = k.split("__")
-        cfg.setdefault(sec, {})[key] = v
-    if cfg.get("seed_everything") not in (None, False):
-        seed_everything(cfg["seed_everything"])
+    cfg = load_config(config, overrides)
     module, trainer = build_style_from_config(cfg)
     data = build_latent_data(dict(cfg["data"]), trainer, style_only=True)
     trainer.fit(module, data, ckpt_path=ckpt_path)
@@ -452,16 +449,7 @@ def build_latent_from_config(cfg: Dict[str, Any]):
     from .latent_train import LatentTrainer
     m = dict(cfg["model"])
     m["schedule_args"] = LRScheduleArgs(**(m.get("schedule_args") or {}))
-    t = dict(cfg.get("trainer", {}))
-    for k in ("callbacks", "logger", "enable_progress_bar", "enable_model_summary", "benchmark"):
-        t.pop(k, None)
-    refuse_accumulation(t, "fit-latent")
-    t.setdefault("monitor", "eval/score")
-    t.setdefault("monitor_mode", "max")
-    t.setdefault("default_root_dir", "runs/latent")
-    if launch.parse_devices(t.get("devices", 1)) > 1:
-        raise RuntimeError(f"fit-latent trains on one device (trainer.devices={t['devices']}): the reference trains the latent model on one "
-                           "GPU, and the gradient exchange (GradBucketReducer) is tied to the denoiser's arena")
+    t = trainer_kwargs(cfg, "fit-latent", monitor="eval/score", monitor_mode="max", default_root_dir="runs/latent")
     module, trainer = LatentTrainer(**m), Trainer(**t)
     if trainer.precision.startswith("bf16"):
         module.latent.compute_dtype = torch.bfloat16        # LatentModel does not follow autocast: its compute type is set here
@@ -475,11 +463,9 @@ def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer", val_pad_multipl
     validates them in ragged groups of at most `data.val_frame_budget` padded frames, each map padded to `val_pad_multiple` (the
     trainer's 2 x chunk_size)."""
     from .data import BeatmapDataModule
-    resident, max_gb = data.pop("resident", False), data.pop("resident_max_gb", None)
     resident_val, val_budget = data.pop("resident_val", False), data.pop("val_frame_budget", None)
-    if not resident:
-        if max_gb is not None:
-            raise ValueError("data.resident_max_gb bounds the resident store: set data.resident: true, or drop the key")
+    resident = pop_resident(data, trainer)
+    if resident is None:
         if resident_val or val_budget is not None:
             raise ValueError("data.resident_val / data.val_frame_budget validate from the resident store: set data.resident: true, or drop "
                              "the keys")
@@ -487,27 +473,13 @@ def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer", val_pad_multipl
     if val_budget is not None and not resident_val:
         raise ValueError("data.val_frame_budget sizes the groups of the resident validation: set data.resident_val: true, or drop the key")
     from .resident import ResidentBeatmapDataModule
-    if data.get("num_workers") and trainer.rank == 0:
-        print(f"data.resident: batches are gathered on the device, data.num_workers={data['num_workers']} is ignored for training")
-    if torch.cuda.is_available():
-        device = torch.device("cuda", trainer.local_rank)
-    elif _lib.loaded_path() not in (None, _lib.DEFAULT_SO):
-        device = torch.device("cpu")         # test-suite only, as in Trainer.fit
-    else:
-        raise RuntimeError("data.resident needs an MI355X: the store lives in device memory")
-    return ResidentBeatmapDataModule(**data, device=device, resident_max_gb=max_gb, resident_val=bool(resident_val),
-                                     val_frame_budget=val_budget, val_pad_multiple=val_pad_multiple)
+    return ResidentBeatmapDataModule(**data, **resident, resident_val=bool(resident_val), val_frame_budget=val_budget,
+                                     val_pad_multiple=val_pad_multiple)
 
 
 def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = None, **overrides):
     """begin a training run for the latent model (reference: scripts/fit_latent.py, models/latent/model.yml)."""
-    with open(config) as f:
-        cfg = yaml.safe_load(f)
-    for k, v in overrides.items():
-        sec, key = k.split("__")
-        cfg.setdefault(sec, {})[key] = v
-    if cfg.get("seed_everything") not in (None, False):
-        seed_everything(cfg["seed_everything"])
+    cfg = load_config(config, overrides)
     module, trainer = build_latent_from_config(cfg)
     data = build_beatmap_data(dict(cfg["data"]), trainer, val_pad_multiple=2 * module.latent.chunk_size)
     trainer.fit(module, data, ckpt_path=ckpt_path)
@@ -517,15 +489,12 @@ def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = N
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="osu_dreamer_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    f = sub.add_parser("fit-denoiser", help="begin a training run for the diffusion model")
-    f.add_argument("-c", "--config", default=DEFAULT_CONFIG)
-    f.add_argument("--ckpt-path", default=None)
-    fs = sub.add_parser("fit-style", help="begin a training run for the style model")
-    fs.add_argument("-c", "--config", default=DEFAULT_STYLE_CONFIG)
-    fs.add_argument("--ckpt-path", default=None)
-    fl = sub.add_parser("fit-latent", help="begin a training run for the latent model")
-    fl.add_argument("-c", "--config", default=DEFAULT_LATENT_CONFIG)
-    fl.add_argument("--ckpt-path", default=None)
+    fits = {"fit-denoiser": ("diffusion", DEFAULT_CONFIG, fit_denoiser), "fit-style": ("style", DEFAULT_STYLE_CONFIG, fit_style),
+            "fit-latent": ("latent", DEFAULT_LATENT_CONFIG, fit_latent)}
+    for cmd, (model, config, _) in fits.items():
+        f = sub.add_parser(cmd, help=f"begin a training run for the {model} model")
+        f.add_argument("-c", "--config", default=config)
+        f.add_argument("--ckpt-path", default=None)
     from . import encode_latents as encode_cmd
     from . import predict as predict_cmd
     encode_cmd.add_parser(sub)
@@ -535,12 +504,6 @@ def main(argv=None):
         return predict_cmd.run(a)
     if a.cmd == "encode-latents":
         return encode_cmd.run(a)
-    if a.cmd == "fit-style":
-        fit_style(a.config, a.ckpt_path)
-        return
-    if a.cmd == "fit-latent":
-        fit_latent(a.config, a.ckpt_path)
-        return
     if a.cmd == "fit-denoiser":
         with open(a.config) as fh:
             cfg = yaml.safe_load(fh)
@@ -551,7 +514,7 @@ def main(argv=None):
                                           module="osu_dreamer_amd")
         if rc is not None:
             raise SystemExit(rc)
-        fit_denoiser(a.config, a.ckpt_path)
+    fits[a.cmd][2](a.config, a.ckpt_path)
 
 
 if __name__ == "__main__":

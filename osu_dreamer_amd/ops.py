@@ -169,14 +169,19 @@ def cl_to_frames(src, dst):
     _lib.lib().od_cl_to_frames(dt_code(dst.dtype), _p(src), _p(dst), _ld(dst), B, C, L, _stream(src))
 
 
+def _feed_rows(base, cstride, lens, N):
+    """The per-row descriptor both feed gathers read on the device: base / cstride int64 [N], lens int32 [N]."""
+    assert lens.dtype == torch.int32 and lens.dim() == 1 and lens.shape[0] == N and lens.is_contiguous(), "lens must be a contiguous int32 [B]"
+    for t in (base, cstride):
+        assert t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == N and t.is_contiguous(), "base / cstride must be contiguous int64 [N]"
+
+
 def feed_gather(store, base, cstride, lens, out):
     """out (N, C, Lpad) fp32 = per row n, lens[n] frames of C channels from the flat fp32 `store` at base[n] + c * cstride[n], zero beyond
     (base, cstride: device int64 [N]; lens: device int32 [N]).  Every element of out is written."""
     N, C, Lpad = out.shape
     _f32(store, out)
-    _lens(lens, N)
-    for t in (base, cstride):
-        assert t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == N and t.is_contiguous(), "base / cstride must be contiguous int64 [N]"
+    _feed_rows(base, cstride, lens, N)
     assert store.device == out.device == base.device == cstride.device == lens.device, "feed_gather: every tensor on one device"
     _lib.lib().od_feed_gather(_p(store), store.numel(), _p(base), _p(cstride), _p(lens), _p(out), N, C, Lpad, _stream(out))
 
@@ -189,10 +194,8 @@ def feed_gather_quant(store, elem_size, base, cstride, lens, out, c0=0, channels
     N, Ctot, Lpad = out.shape
     C = Ctot - c0 if channels is None else channels
     _f32(out)
-    _lens(lens, N)
+    _feed_rows(base, cstride, lens, N)
     assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous(), "the store is a flat uint8 tensor (its bytes)"
-    for t in (base, cstride):
-        assert t.dtype == torch.int64 and t.dim() == 1 and t.shape[0] == N and t.is_contiguous(), "base / cstride must be contiguous int64 [N]"
     assert (scale is None) == (offset is None), "scale and offset come together"
     for t in (scale, offset):
         assert t is None or (t.dtype == torch.float64 and tuple(t.shape) == (N, C) and t.is_contiguous()), "scale / offset must be contiguous fp64 (N, channels)"

@@ -30,16 +30,12 @@ from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .data import (A_DIM, NUM_LABELS, X_DIM, Batch, BeatmapDataModule, BeatmapDataset, LatentBatch, LatentDataModule, LatentDataset,
-                   RaggedBeatmapBatch, RaggedLatentBatch, cut_batches)
+                   RaggedBeatmapBatch, RaggedLatentBatch, _roundup, cut_batches)
 
 ALL_FIELDS = ("h", "z", "s", "labels")
 STYLE_FIELDS = ("s", "labels")
-
-
-def _roundup(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 def _read_header(f) -> Tuple[Tuple[int, ...], np.dtype]:
@@ -61,16 +57,6 @@ def npy_header(path) -> Tuple[Tuple[int, ...], np.dtype]:
         return _read_header(f)
 
 
-def npz_member_shape(path, member: str) -> Tuple[int, ...]:
-    """Shape of `member` of an .npz, from the member's .npy header (the array is not read)."""
-    return npz_member_header(path, member)[0]
-
-
-def npy_shape(path) -> Tuple[int, ...]:
-    """Shape of an .npy file, from its header (the array is not read or mapped)."""
-    return npy_header(path)[0]
-
-
 def shard_files(mapsets: Sequence[Path], rank: int = 0, world_size: int = 1) -> List[Path]:
     """The rank's share of the dataset: files in `LatentDataset._files()` order, file i to rank i % world_size (the host loader's rank shard)."""
     return [f for i, f in enumerate(LatentDataset(list(mapsets))._files()) if i % world_size == rank]
@@ -79,11 +65,14 @@ def shard_files(mapsets: Sequence[Path], rank: int = 0, world_size: int = 1) -> 
 # ------------------------------------------------------------------------------------------------------------------------------ the plan
 class PlanBatch(NamedTuple):
     """One batch of an epoch plan, host integers only: row i takes frames starts[i] .. starts[i] + lens[i] of map maps[i] (an index into the
-    store's files); Lpad is the batch's padded length (= seq_len for fixed windows)."""
+    store's files); Lpad is the batch's padded length (= seq_len for fixed windows).  The beatmap feed adds each window's flip
+    augmentation: bit FLIP_X / FLIP_Y of flips[i] set = cursor x / y of row i is mirrored (v <- 1 - v), each with probability 1/2
+    (BeatmapDataset.make_samples)."""
     maps: np.ndarray       # (B,) int64
     starts: np.ndarray     # (B,) int64
     lens: np.ndarray       # (B,) int64
     Lpad: int
+    flips: Optional[np.ndarray] = None     # (B,) int32
 
 
 class EpochPlanner:
@@ -175,6 +164,27 @@ class EpochPlanner:
 
 
 # ----------------------------------------------------------------------------------------------------------------------------- the store
+def _refuse_over_limit(nbytes: int, n: int, max_bytes: Optional[int], reserved_bytes: int = 0):
+    """MemoryError for a store of `nbytes` for `n` maps that does not fit under `max_bytes` beside the `reserved_bytes` another store under
+    the same limit already holds.  The stores call it with sizes read from headers: before anything is allocated or any array read."""
+    if max_bytes is None or nbytes + reserved_bytes <= max_bytes:
+        return
+    limit = f"the limit of {int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or "
+    if reserved_bytes:
+        raise MemoryError(f"the resident store of the held-out maps needs {nbytes} bytes for {n} maps beside the training store's "
+                          f"{int(reserved_bytes)}: together more than {limit}validate with data.resident_val: false")
+    raise MemoryError(f"the resident store needs {nbytes} bytes ({nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than {limit}train with "
+                      "data.resident: false")
+
+
+def _device_or_default(device) -> torch.device:
+    return torch.device(device) if device is not None else _lib.training_device(None, "data.resident")
+
+
+def _gb_to_bytes(gb: Optional[float]) -> Optional[int]:
+    return None if gb is None else int(float(gb) * 2 ** 30)
+
+
 class ResidentLatentStore:
     """The rank's share of an encoded dataset on `device`, every file read once.
 
@@ -199,9 +209,9 @@ class ResidentLatentStore:
         if not self.files:
             raise ValueError(f"no *.latent.npz file for rank {rank} of {world_size}")
         # ---- sizes from the headers
-        z_shapes = [npz_member_shape(f, "z") for f in self.files]
+        z_shapes = [npz_member_header(f, "z")[0] for f in self.files]
         self.lengths = np.asarray([sh[-1] for sh in z_shapes], dtype=np.int64)
-        self.style_dim = int(np.prod(npz_member_shape(self.files[0], "s")))
+        self.style_dim = int(np.prod(npz_member_header(self.files[0], "s")[0]))
         self.emb_dim = int(z_shapes[0][0])
         n = len(self.files)
         self.h_base, self.h_stride = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
@@ -214,7 +224,7 @@ class ResidentLatentStore:
             for i, f in enumerate(self.files):
                 d = f.parent
                 if d not in seen:
-                    A, Lh = npy_shape(d / "h.npy")
+                    A, Lh = npy_header(d / "h.npy")[0]
                     self.a_dim = self.a_dim or A
                     if A != self.a_dim:
                         raise ValueError(f"{d / 'h.npy'}: {A} channels, the dataset's other maps have {self.a_dim}")
@@ -228,9 +238,7 @@ class ResidentLatentStore:
                 self.z_base[i] = elems
                 elems += self.emb_dim * int(self.lengths[i])
         self.nbytes = 4 * (elems + n * (self.style_dim + NUM_LABELS))
-        if max_bytes is not None and self.nbytes > max_bytes:
-            raise MemoryError(f"the resident store needs {self.nbytes} bytes ({self.nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than the limit of "
-                              f"{int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or train with data.resident: false")
+        _refuse_over_limit(self.nbytes, n, max_bytes)
         # ---- allocate and fill
         self.data = torch.empty(max(elems, 1), dtype=torch.float32, device=self.device)
         s_host, labels_host = np.empty((n, self.style_dim), dtype=np.float32), np.empty((n, NUM_LABELS), dtype=np.float32)
@@ -287,12 +295,54 @@ class _Uploader:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the feed
-class ResidentFeed:
-    """Re-iterable over the batches of one epoch each: every iter() draws a new plan from the feed's generator — seeded, at the first epoch,
-    like LatentDataset.__iter__ (torch.initial_seed() + 7919 * rank) — and yields the plan's batches, built on the device."""
+def pack_descriptors(device, pin: bool, i64: Sequence[np.ndarray] = (), f64: Sequence[np.ndarray] = (), i32: Sequence[np.ndarray] = ()):
+    """The device views of a batch's host columns, in the order given, behind ONE stream-ordered copy: the columns fill one host block
+    (pinned when `pin`) — the 8-byte ones first, so that every fp64 view stays 8-byte aligned, the int32 ones behind them — and one
+    device block takes it.  A view has its column's shape.  The pinned block returns to torch's host allocator, which hands it out again
+    only after that copy has run."""
+    n8, n4 = 0, 0                                   # plain loops throughout: this runs per batch, on a launch-bound path
+    for c in i64:
+        n8 += c.size
+    for c in f64:
+        n8 += c.size
+    for c in i32:
+        n4 += c.size
+    host = torch.empty(n8 + (n4 + 1) // 2, dtype=torch.int64, pin_memory=pin)
+    hv = host.numpy()
+    desc = torch.empty(host.numel(), dtype=torch.int64, device=device)
+    views, o = [], 0
+    for c in i64:
+        e = o + c.size
+        hv[o:e] = c
+        views.append(desc[o:e])
+        o = e
+    for c in f64:
+        e = o + c.size
+        hv[o:e].view(np.float64)[:] = c.reshape(-1)
+        views.append(desc[o:e].view(torch.float64).view(c.shape))
+        o = e
+    if i32:
+        h32, d32, o = hv[n8:].view(np.int32), desc[n8:].view(torch.int32), 0
+        for c in i32:
+            e = o + c.size
+            h32[o:e] = c
+            views.append(d32[o:e])
+            o = e
+    desc.copy_(host, non_blocking=True)
+    return views
 
-    def __init__(self, store: ResidentLatentStore, planner: EpochPlanner, ragged: bool, rank: int = 0):
-        self.store, self.planner, self.ragged, self.rank = store, planner, ragged, rank
+
+def _assert_inside_maps(map_lens: np.ndarray, starts: np.ndarray, lens: np.ndarray, Lpad: int):
+    # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
+    assert (starts >= 0).all() and (lens >= 1).all() and (lens <= Lpad).all() and (starts + lens <= map_lens).all()
+
+
+class _EpochFeed:
+    """Re-iterable over the batches of one epoch each: every iter() draws a new plan from the feed's generator — seeded, at the first epoch,
+    like the host datasets' __iter__ (torch.initial_seed() + 7919 * rank) — and yields the plan's batches, built on the device by gather()."""
+
+    def __init__(self, store, planner: EpochPlanner, rank: int = 0):
+        self.store, self.planner, self.rank = store, planner, rank
         self.gen: Optional[torch.Generator] = None
         self.pin = store.device.type == "cuda"
 
@@ -301,42 +351,40 @@ class ResidentFeed:
             self.gen = torch.Generator().manual_seed(torch.initial_seed() + 7919 * self.rank)
         return self.planner.plan(self.gen)
 
+    def __iter__(self) -> Iterator:
+        for pb in self.plan_epoch():
+            yield self.gather(pb)
+
+
+class ResidentFeed(_EpochFeed):
+    """The feed of the encoded dataset (ResidentLatentStore): LatentBatch, or RaggedLatentBatch when `ragged`."""
+
+    def __init__(self, store: ResidentLatentStore, planner: EpochPlanner, ragged: bool, rank: int = 0):
+        super().__init__(store, planner, rank)
+        self.ragged = ragged
+
     def gather(self, pb: PlanBatch):
         """The device batch of one plan entry: h and z by od_feed_gather, s and labels by index_select.  The descriptors (h base, h channel
-        stride, z base, z channel stride, map index as int64, the lengths as int32 behind them) travel as ONE stream-ordered copy from pinned
-        memory; the pinned block returns to torch's host allocator, which hands it out again only after that copy has run."""
+        stride, z base, z channel stride, map index as int64, the lengths as int32) travel as one copy (pack_descriptors)."""
         st, B = self.store, len(pb.maps)
         if st.has_frames:
-            # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
-            assert (pb.starts >= 0).all() and (pb.lens >= 1).all() and (pb.lens <= pb.Lpad).all() and (pb.starts + pb.lens <= st.lengths[pb.maps]).all()
-            host = torch.empty(5 * B + (B + 1) // 2, dtype=torch.int64, pin_memory=self.pin)
-            hv = host.numpy()
-            hv[0:B], hv[B:2 * B] = st.h_base[pb.maps] + pb.starts, st.h_stride[pb.maps]
-            hv[2 * B:3 * B], hv[3 * B:4 * B] = st.z_base[pb.maps] + pb.starts, st.lengths[pb.maps]
-            hv[4 * B:5 * B] = pb.maps
-            hv[5 * B:].view(np.int32)[:B] = pb.lens
-            desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
-            desc.copy_(host, non_blocking=True)
-            maps, lens32 = desc[4 * B:5 * B], desc[5 * B:].view(torch.int32)[:B]
+            map_lens = st.lengths[pb.maps]                      # z's channel stride
+            _assert_inside_maps(map_lens, pb.starts, pb.lens, pb.Lpad)
+            h_base, h_stride, z_base, z_stride, maps, lens32 = pack_descriptors(
+                st.device, self.pin, i64=(st.h_base[pb.maps] + pb.starts, st.h_stride[pb.maps], st.z_base[pb.maps] + pb.starts, map_lens,
+                                          pb.maps), i32=(pb.lens,))
             h = torch.empty(B, st.a_dim, pb.Lpad, dtype=torch.float32, device=st.device)
             z = torch.empty(B, st.emb_dim, pb.Lpad, dtype=torch.float32, device=st.device)
-            ops.feed_gather(st.data, desc[0:B], desc[B:2 * B], lens32, h)
-            ops.feed_gather(st.data, desc[2 * B:3 * B], desc[3 * B:4 * B], lens32, z)
+            ops.feed_gather(st.data, h_base, h_stride, lens32, h)
+            ops.feed_gather(st.data, z_base, z_stride, lens32, z)
         else:
-            host = torch.from_numpy(np.ascontiguousarray(pb.maps))
-            if self.pin:
-                host = host.pin_memory()
-            maps = host.to(st.device, non_blocking=True)
+            maps, = pack_descriptors(st.device, self.pin, i64=(pb.maps,))
             h = torch.empty(B, 0, pb.Lpad, dtype=torch.float32, device=st.device)      # the style model reads s and labels only
             z = torch.empty(B, 0, pb.Lpad, dtype=torch.float32, device=st.device)
         s, labels = st.s.index_select(0, maps), st.labels.index_select(0, maps)
         if self.ragged:
             return RaggedLatentBatch(h, z, s, labels, torch.from_numpy(pb.lens.astype(np.int64)))
         return LatentBatch(h, z, s, labels)
-
-    def __iter__(self) -> Iterator:
-        for pb in self.plan_epoch():
-            yield self.gather(pb)
 
 
 class ResidentLatentDataModule:
@@ -352,11 +400,9 @@ class ResidentLatentDataModule:
         # the host module validates the keys, holds out the validation mapsets and keeps the validation loader
         self.host = LatentDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
                                      rank, world_size, max_len, pad_multiple, batch_frames, bucket_pool)
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device, self.fields = torch.device(device), tuple(fields)
+        self.device, self.fields = _device_or_default(device), tuple(fields)
         self.ragged, self.rank = self.host.ragged, rank
-        max_bytes = None if resident_max_gb is None else int(float(resident_max_gb) * 2 ** 30)
+        max_bytes = _gb_to_bytes(resident_max_gb)
         self.store = ResidentLatentStore(self.host.train_set.mapsets, self.device, self.fields, rank, world_size, max_bytes)
         self.planner = EpochPlanner(self.store.lengths, batch_size, seq_len, max_per_map, max_len, pad_multiple, self.host.batch_frames,
                                     self.host.bucket_pool)
@@ -385,16 +431,6 @@ class ResidentLatentDataModule:
 # ------------------------------------------------------------------------------------------- the latent model's feed: quantised beatmaps
 HIT_DIM = X_DIM - 2                    # chart rows 0..6 come from `hit` (uint8), rows 7, 8 (cursor x, y) from `xy` (uint16)
 FLIP_X, FLIP_Y = 1, 2                  # bits of a window's flip mask = bits of od_feed_gather_quant's mask over the two xy channels
-
-
-class BeatmapPlanBatch(NamedTuple):
-    """PlanBatch of fixed windows with each window's flip augmentation: bit FLIP_X / FLIP_Y of flips[i] set = cursor x / y of row i is
-    mirrored (v <- 1 - v), each with probability 1/2 (BeatmapDataset.make_samples)."""
-    maps: np.ndarray       # (B,) int64
-    starts: np.ndarray     # (B,) int64
-    lens: np.ndarray       # (B,) int64
-    Lpad: int
-    flips: np.ndarray      # (B,) int32
 
 
 class ResidentBeatmapStore:
@@ -459,13 +495,7 @@ class ResidentBeatmapStore:
             self.xy_base[i] = nbytes // 2
             nbytes += 2 * 2 * int(self.lengths[i])
         self.nbytes = nbytes + 4 * n * NUM_LABELS
-        if max_bytes is not None and reserved_bytes and self.nbytes + reserved_bytes > max_bytes:
-            raise MemoryError(f"the resident store of the held-out maps needs {self.nbytes} bytes for {n} maps beside the training store's "
-                              f"{int(reserved_bytes)}: together more than the limit of {int(max_bytes)} bytes (data.resident_max_gb = "
-                              f"{max_bytes / 2 ** 30:.2f}): raise the limit, or validate with data.resident_val: false")
-        if max_bytes is not None and self.nbytes > max_bytes:
-            raise MemoryError(f"the resident store needs {self.nbytes} bytes ({self.nbytes / 2 ** 30:.2f} GiB) for {n} maps, more than the limit of "
-                              f"{int(max_bytes)} bytes (data.resident_max_gb = {max_bytes / 2 ** 30:.2f}): raise the limit, or train with data.resident: false")
+        _refuse_over_limit(self.nbytes, n, max_bytes, reserved_bytes)
         # ---- allocate and fill
         self.data = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.xy_rng, self.xy_min = np.empty((n, 2), dtype=np.float64), np.empty((n, 2), dtype=np.float64)
@@ -489,66 +519,46 @@ class ResidentBeatmapStore:
 def gather_beatmap_rows(st: ResidentBeatmapStore, pin: bool, maps: np.ndarray, starts: np.ndarray, lens: np.ndarray, Lpad: int,
                         aux: np.ndarray, flip: bool):
     """(audio (B, 72, Lpad), chart (B, 9, Lpad), the maps' indices, lens and aux as device int32): row i takes lens[i] frames of map
-    maps[i] from frame starts[i], zeros behind.  Everything the three od_feed_gather_quant launches read per row travels as ONE
-    stream-ordered copy from pinned memory, 11 B 64-bit words: the spectrogram's base and channel stride, the hit and xy bases, the
-    chart's channel stride, the map index (for the labels), xy_rng and xy_min as fp64 (B, 2) each, then the lengths and `aux` as int32.
+    maps[i] from frame starts[i], zeros behind.  Everything the three od_feed_gather_quant launches read per row travels as one copy
+    (pack_descriptors), 11 B 64-bit words: the spectrogram's base and channel stride, the hit and xy bases, the chart's channel stride,
+    the map index (for the labels), xy_rng and xy_min as fp64 (B, 2) each, then the lengths and `aux` as int32.
     `aux` (B,) is the rows' flip masks when `flip`, else whatever int32 the caller wants on the device beside the lengths."""
     B = len(maps)
-    # a descriptor outside the store would be caught by the kernel (NaN rows); a plan that leaves its map is a bug to stop here
-    assert (starts >= 0).all() and (lens >= 1).all() and (lens <= Lpad).all() and (starts + lens <= st.lengths[maps]).all()
-    host = torch.empty(11 * B, dtype=torch.int64, pin_memory=pin)
-    hv = host.numpy()
-    hv[0:B], hv[B:2 * B] = st.spec_base[maps] + starts, st.spec_stride[maps]
-    hv[2 * B:3 * B], hv[3 * B:4 * B] = st.hit_base[maps] + starts, st.xy_base[maps] + starts
-    hv[4 * B:5 * B], hv[5 * B:6 * B] = st.lengths[maps], maps
-    hv[6 * B:8 * B].view(np.float64)[:] = st.xy_rng[maps].reshape(-1)
-    hv[8 * B:10 * B].view(np.float64)[:] = st.xy_min[maps].reshape(-1)
-    i32 = hv[10 * B:].view(np.int32)
-    i32[:B], i32[B:] = lens, aux
-    desc = torch.empty(host.numel(), dtype=torch.int64, device=st.device)
-    desc.copy_(host, non_blocking=True)
-    rng, lo = desc[6 * B:8 * B].view(torch.float64).view(B, 2), desc[8 * B:10 * B].view(torch.float64).view(B, 2)
-    d32 = desc[10 * B:].view(torch.int32)
-    lens32, aux32 = d32[:B], d32[B:]
+    map_lens = st.lengths[maps]                                 # the chart's channel stride
+    _assert_inside_maps(map_lens, starts, lens, Lpad)
+    spec_base, spec_stride, hit_base, xy_base, stride, idx, rng, lo, lens32, aux32 = pack_descriptors(
+        st.device, pin, i64=(st.spec_base[maps] + starts, st.spec_stride[maps], st.hit_base[maps] + starts, st.xy_base[maps] + starts,
+                             map_lens, maps), f64=(st.xy_rng[maps], st.xy_min[maps]), i32=(lens, aux))
     audio = torch.empty(B, A_DIM, Lpad, dtype=torch.float32, device=st.device)
     chart = torch.empty(B, X_DIM, Lpad, dtype=torch.float32, device=st.device)
-    ops.feed_gather_quant(st.data, 1, desc[0:B], desc[B:2 * B], lens32, audio)
-    ops.feed_gather_quant(st.data, 1, desc[2 * B:3 * B], desc[4 * B:5 * B], lens32, chart, c0=0, channels=HIT_DIM)
-    ops.feed_gather_quant(st.data, 2, desc[3 * B:4 * B], desc[4 * B:5 * B], lens32, chart, c0=HIT_DIM, channels=2, scale=rng, offset=lo,
+    ops.feed_gather_quant(st.data, 1, spec_base, spec_stride, lens32, audio)
+    ops.feed_gather_quant(st.data, 1, hit_base, stride, lens32, chart, c0=0, channels=HIT_DIM)
+    ops.feed_gather_quant(st.data, 2, xy_base, stride, lens32, chart, c0=HIT_DIM, channels=2, scale=rng, offset=lo,
                           flip=aux32 if flip else None)
-    return audio, chart, desc[5 * B:6 * B], lens32, aux32
+    return audio, chart, idx, lens32, aux32
 
 
-class ResidentBeatmapFeed:
-    """Re-iterable over the batches of one epoch each, as ResidentFeed: every iter() draws a new plan — the windows by EpochPlanner's
-    fixed-window rule on the chart lengths (BeatmapDataset.make_samples' rule), then the two flips of every window — from the feed's
-    generator, seeded at the first epoch like the host dataset (torch.initial_seed() + 7919 * rank), and yields `data.Batch`es built on the
-    device by three od_feed_gather_quant launches."""
+class ResidentBeatmapFeed(_EpochFeed):
+    """The feed of the pre-processed beatmaps (ResidentBeatmapStore): the windows by EpochPlanner's fixed-window rule on the chart lengths
+    (BeatmapDataset.make_samples' rule), then the two flips of every window, and `data.Batch`es built on the device by three
+    od_feed_gather_quant launches."""
 
     def __init__(self, store: ResidentBeatmapStore, planner: EpochPlanner, rank: int = 0):
         if planner.seq_len is None:
             raise ValueError("the resident beatmap feed cuts fixed windows: it needs an integer seq_len")
-        self.store, self.planner, self.rank = store, planner, rank
-        self.gen: Optional[torch.Generator] = None
-        self.pin = store.device.type == "cuda"
+        super().__init__(store, planner, rank)
 
-    def plan_epoch(self) -> List[BeatmapPlanBatch]:
-        if self.gen is None:
-            self.gen = torch.Generator().manual_seed(torch.initial_seed() + 7919 * self.rank)
-        plan = self.planner.plan(self.gen)
+    def plan_epoch(self) -> List[PlanBatch]:
+        plan = super().plan_epoch()
         B = self.planner.batch_size
         draws = (torch.rand(len(plan) * B, 2, generator=self.gen) < 0.5).numpy()
         flips = (draws[:, 0] * FLIP_X + draws[:, 1] * FLIP_Y).astype(np.int32)
-        return [BeatmapPlanBatch(pb.maps, pb.starts, pb.lens, pb.Lpad, flips[i * B:(i + 1) * B]) for i, pb in enumerate(plan)]
+        return [pb._replace(flips=flips[i * B:(i + 1) * B]) for i, pb in enumerate(plan)]
 
-    def gather(self, pb: BeatmapPlanBatch) -> Batch:
+    def gather(self, pb: PlanBatch) -> Batch:
         """The device batch of one plan entry (gather_beatmap_rows with the windows' flip masks)."""
         audio, chart, idx, _, _ = gather_beatmap_rows(self.store, self.pin, pb.maps, pb.starts, pb.lens, pb.Lpad, pb.flips, flip=True)
         return Batch(audio, chart, self.store.labels.index_select(0, idx))
-
-    def __iter__(self) -> Iterator[Batch]:
-        for pb in self.plan_epoch():
-            yield self.gather(pb)
 
 
 class ResidentBeatmapValFeed:
@@ -641,10 +651,8 @@ class ResidentBeatmapDataModule:
                              "is needed")
         self.host = BeatmapDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
                                       rank, world_size)
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device, self.rank = torch.device(device), rank
-        max_bytes = None if resident_max_gb is None else int(float(resident_max_gb) * 2 ** 30)
+        self.device, self.rank = _device_or_default(device), rank
+        max_bytes = _gb_to_bytes(resident_max_gb)
         self.store = ResidentBeatmapStore(self.host.train_set.mapsets, self.device, rank, world_size, max_bytes)
         self.planner = EpochPlanner(self.store.lengths, batch_size, int(seq_len), max_per_map)
         self.feed = ResidentBeatmapFeed(self.store, self.planner, rank)

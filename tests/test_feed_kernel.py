@@ -124,15 +124,34 @@ def test_descriptor_outside_the_store_is_not_loaded(dev):
     C, Lpad = 2, 8
     store = _store(40, 29)
     st = torch.from_numpy(store).to(dev)
-    out = Flat((4, C, Lpad), dev)
-    base = torch.tensor([0, 30, -4, 0], dtype=torch.int64, device=dev)      # row 1: channel 1 would end at 30 + 8 + 5 = 43 > 40
-    cstride = torch.tensor([8, 8, 8, 8], dtype=torch.int64, device=dev)
-    lens = torch.tensor([8, 5, 4, 9], dtype=torch.int32, device=dev)       # row 3: len > Lpad
+    out = Flat((5, C, Lpad), dev)
+    base = torch.tensor([0, 30, -4, 0, 0], dtype=torch.int64, device=dev)   # row 1: channel 1 would end at 30 + 8 + 5 = 43 > 40
+    cstride = torch.tensor([8, 8, 8, 8, 2 ** 62], dtype=torch.int64, device=dev)       # row 4: a stride no store holds
+    lens = torch.tensor([8, 5, 4, 9, 4], dtype=torch.int32, device=dev)    # row 3: len > Lpad
     ops.feed_gather(st, base, cstride, lens, out.v)
     got = out.v.cpu()
     assert np.array_equal(got[0].numpy(), store[:16].reshape(2, 8))
     assert np.array_equal(got[1, 0, :5].numpy(), store[30:35]) and bool((got[1, 0, 5:] == 0).all())     # channel 0 lies inside
     assert bool(torch.isnan(got[1, 1]).all()) and bool(torch.isnan(got[2]).all()) and bool(torch.isnan(got[3]).all())
+    assert bool(torch.isnan(got[4]).all())
+    assert bool(torch.isnan(out.buf[:64]).all() & torch.isnan(out.buf[64 + out.n:]).all())
+
+
+@pytest.mark.parametrize("C, stride", [(5, 2 ** 62), (9, 2 ** 61)])
+def test_a_stride_whose_product_wraps_is_not_gathered(dev, C, stride):
+    """(C - 1) * stride = 2^64 wraps to 0: the last channel's offset would pass a test made after the product and gather channel 0's
+    frames.  The stride is checked against the store first, so the whole row is NaN; its ordinary neighbour is gathered bit for bit.
+    Nothing outside the 64-element store is loaded either way."""
+    Lpad = 8
+    store = _store(64, 37)
+    st = torch.from_numpy(store).to(dev)
+    out = Flat((2, C, Lpad), dev)
+    ops.feed_gather(st, torch.tensor([1, 3], dtype=torch.int64, device=dev), torch.tensor([7, stride], dtype=torch.int64, device=dev),
+                    torch.tensor([6, 4], dtype=torch.int32, device=dev), out.v)
+    got = out.v.cpu().numpy()
+    want = _expected(store, [1], [7], [6], C, Lpad)
+    assert np.array_equal(got[:1].view(np.int32), want.view(np.int32))
+    assert np.isnan(got[1]).all(), np.argwhere(~np.isnan(got[1]))[:4]
     assert bool(torch.isnan(out.buf[:64]).all() & torch.isnan(out.buf[64 + out.n:]).all())
 
 

@@ -156,3 +156,22 @@ def test_a_store_over_the_limit_raises_before_it_allocates(dev, tree, monkeypatc
 def test_the_denoiser_validates_on_the_host_loader(dev, tree):
     val = list(_module(tree, dev).val_dataloader())
     assert len(val) == 1 and val[0][1].shape == (1, E, 8) and val[0][0].device.type == "cpu"
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_packed_descriptors_are_views_of_one_block(B):
+    """pack_descriptors, host only: every column comes back as a view of ONE block (one copy took them all), in the order given, with its
+    values and shape; the fp64 views start on 8-byte boundaries — the int32 columns lie behind every 8-byte one — also at an odd B."""
+    rng = np.random.default_rng(B)
+    i64 = [rng.integers(-2 ** 40, 2 ** 40, B) for _ in range(3)]
+    f64 = [rng.standard_normal((B, 2)) for _ in range(2)]
+    i32 = [rng.integers(0, 2 ** 20, B) for _ in range(2)]               # int64 host columns, as a plan's lens are
+    views = resident.pack_descriptors(torch.device("cpu"), False, i64=i64, f64=f64, i32=i32)
+    assert len(views) == 7 and len({v.untyped_storage().data_ptr() for v in views}) == 1
+    assert views[0].untyped_storage().nbytes() == 8 * (3 * B + 4 * B + (2 * B + 1) // 2)
+    for v, c, dt in zip(views, i64 + f64 + i32, [torch.int64] * 3 + [torch.float64] * 2 + [torch.int32] * 2):
+        assert v.dtype == dt and tuple(v.shape) == c.shape and np.array_equal(v.numpy(), c.astype(v.numpy().dtype)), (dt, c)
+    assert all(v.data_ptr() % 8 == 0 for v in views[:5])
+    assert [v.data_ptr() for v in views] == sorted(v.data_ptr() for v in views)
+    only, = resident.pack_descriptors(torch.device("cpu"), False, i64=i64[:1])      # the style feed's one column
+    assert only.dtype == torch.int64 and np.array_equal(only.numpy(), i64[0])

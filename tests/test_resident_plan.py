@@ -1,4 +1,6 @@
 """The resident feed's epoch plan (osu_dreamer_amd/resident.py: EpochPlanner, shard_files): host integers only, no kernel, no store."""
+import hashlib
+import types
 from pathlib import Path
 
 import numpy as np
@@ -6,6 +8,7 @@ import pytest
 import torch
 
 from osu_dreamer_amd.resident import EpochPlanner, shard_files
+from osu_dreamer_amd.resident import ResidentBeatmapFeed
 
 # 48 lengths of 20 .. 600 frames in a scrambled order, two too short for a 152-frame window, one of them empty
 LENGTHS = [20 + (i * 37 % 59) * 10 for i in range(46)] + [0, 151]
@@ -98,3 +101,55 @@ def test_rank_shards_are_disjoint_and_cover_the_files(tmp_path):
         assert sorted(sum(shards, [])) == sorted(names) and sum(len(s) for s in shards) == len(names)
         assert all(s == names[r::world] for r, s in enumerate(shards))
         assert all(isinstance(f, Path) for s in shards for f in s)
+
+
+# ---- the plans themselves: recorded from this file's helper, so that a change to the feed or the planner that moves one draw shows up
+PLAN_LENGTHS = [70, 131, 120, 40, 9, 200]
+PLAN_MODES = {
+    "windows": dict(batch_size=2, seq_len=8),
+    "windows_two_per_map": dict(batch_size=3, seq_len=37, max_per_map=2),
+    "windows_one_per_map": dict(batch_size=2, seq_len=8, max_per_map=1),
+    "chunks": dict(batch_size=2, seq_len=None, max_len=100, pad_multiple=64),
+    "bucketed": dict(batch_size=4, seq_len=None, max_len=128, pad_multiple=64, batch_frames=256, bucket_pool=4),
+}
+# per mode and epoch: (batches, digest)
+PLAN_EXPECTED = {
+    "windows": [(33, "b6b35d528128c758"), (33, "59a9fc23156de9a7")],
+    "windows_two_per_map": [(2, "8d92f5bd704d45ca"), (2, "7256cc9abaf3418a")],
+    "windows_one_per_map": [(3, "dc3d683bf7dc1fba"), (3, "33a6f3e99563d238")],
+    "chunks": [(3, "4c156ec0ede1c9e3"), (3, "6fdd0b4d2f2c9f2a")],
+    "bucketed": [(3, "8fbd132f739e2cd0"), (3, "0e0f0c92274a7b23")],
+}
+BEATMAP_FEED_EXPECTED = [(33, "a5b622a4fcaa518e"), (33, "7f4949eca59e3fbf")]
+
+
+def _plan_digest(plan):
+    """(batches, sha256 over every batch's maps, starts, lens as int64, Lpad, and its flips as int32 where it has them)."""
+    h = hashlib.sha256()
+    for pb in plan:
+        for a in (pb.maps, pb.starts, pb.lens):
+            h.update(np.ascontiguousarray(a, dtype=np.int64).tobytes())
+        h.update(np.int64(pb.Lpad).tobytes())
+        if getattr(pb, "flips", None) is not None:
+            h.update(b"flips" + np.ascontiguousarray(pb.flips, dtype=np.int32).tobytes())
+    return len(plan), h.hexdigest()[:16]
+
+
+@pytest.mark.parametrize("mode", sorted(PLAN_MODES))
+def test_the_plans_of_a_seed_are_the_recorded_ones(mode):
+    gen = _gen(1234)
+    planner = EpochPlanner(PLAN_LENGTHS, **PLAN_MODES[mode])
+    got = [_plan_digest(planner.plan(gen)) for _ in range(2)]
+    assert got == PLAN_EXPECTED[mode]
+
+
+def test_the_beatmap_feed_at_rank_one_plans_the_recorded_windows_and_flips():
+    """The feed seeds its generator with torch.initial_seed() + 7919 * rank at the first epoch and draws every window's two flips behind
+    the planner's draws; the store plays no part in a plan."""
+    torch.manual_seed(1234)
+    store = types.SimpleNamespace(device=torch.device("cpu"))
+    feed = ResidentBeatmapFeed(store, EpochPlanner(PLAN_LENGTHS, batch_size=2, seq_len=8), rank=1)
+    plans = [feed.plan_epoch() for _ in range(2)]
+    assert all(pb.flips.dtype == np.int32 and pb.flips.shape == (2,) and ((pb.flips >= 0) & (pb.flips <= 3)).all() for p in plans for pb in p)
+    got = [_plan_digest(p) for p in plans]
+    assert got == BEATMAP_FEED_EXPECTED
