@@ -1402,6 +1402,12 @@ int launch_tn(const T* G, int ldg, const T* A, int lda, float* dW, int lddw, flo
 
 }  // namespace
 
+// Alignment.  The operands are read in 16-byte chunks: lda, ldw and K must be multiples of one chunk (8 bf16 / 4 fp32 elements; OD_ERR_ALIGN
+// otherwise), and A and W 16-byte aligned.  The OUTPUT has no such rule: any ldc >= N and any N are taken.  When N and ldc are both
+// multiples of 8 every kernel stores (and, with accumulate, reloads) 8-element groups in 16-byte pieces, which then needs C and the bias
+// 16-byte aligned; otherwise (the latent model's score GEMM: N = ldc = 2, a 4-byte bf16 row) gemm_nt_kernel stores, reloads and
+// adds the bias element by element, C needs only its element's alignment, and the 256 x 256 kernels are not selected.  Either way nothing
+// outside C[m][0..N) of the M rows is read or written.  tests/test_gemm_narrow_paths.py runs ldc = N = 2 and 16 in both output types.
 extern "C" int od_gemm_nt(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc,
                           int M, int N, int K, int epilogue, int accumulate, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0) return OD_ERR_ARG;

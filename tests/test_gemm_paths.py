@@ -35,7 +35,9 @@ Every case runs with the deterministic shadow off; the TN and colsum cases also 
 Memory contract: every output sits inside a wider NaN-prefilled buffer (non-zero column offset, ldc > N, rows past M), every operand inside
 a NaN-poisoned one (columns K..lda of A and W, rows past M and N).  Afterwards every element outside the output is still NaN and none
 inside is.  A kernel that reads outside its operand — or masks such a read by multiplying it with zero — fails, and so does one that writes
-outside [M, N] or leaves an element unwritten.
+outside [M, N] or leaves an element unwritten.  A second layout (`NT.layout = "model"`, `TN.ldg` / `TN.lda`; tests/test_gemm_narrow_paths.py
+runs it) is what LatentModel passes: contiguous operands and output, lda = ldw = K and ldc = N exactly (TN: chosen leading dimensions, NaN in
+columns N..ldg and K..lda), each with 64 NaN elements either side.
 
 Input families (built in fp32, rounded to the operand type; the reference reads the rounded operands back):
   integer       small integers (+-1, sparse enough that |C| <= 256): every product and sum is exact in fp32 and in bf16, so every path without
@@ -235,7 +237,7 @@ def make_nt_inputs(fam, M, N, K, device, bias=True, acc=False, seed=0):
         h = K // 2
         A = (rn(M, h).double() @ Q[:, :h].t()).float() + 1e-3 * rn(M, K)
         W = (rn(N, K - h).double() @ Q[:, h:].t()).float() + 1e-3 * rn(N, K)
-        b = c0 = None
+        b, c0 = None, 1e-3 * c0 if acc else None          # accumulate: onto values of C's own size
     elif fam == "lo_matters":
         def lo(rows):
             u = 1 + torch.randint(0, 128, (rows, K), generator=g, device=device).float() / 128      # bf16-exact, [1, 2)
@@ -279,6 +281,25 @@ def bits(t):
     return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
 
 
+def flat_buffer(shape, dtype, device, fill=None):
+    """The `model` layout: a contiguous tensor of `shape` (NaN, or a copy of `fill`) with 64 NaN elements either side; returns (buffer, view)."""
+    n = math.prod(shape)
+    buf = torch.full((n + 128,), NAN, dtype=dtype, device=device)
+    v = buf[64:64 + n].view(*shape)
+    if fill is not None:
+        v.copy_(fill)
+    return buf, v
+
+
+def assert_flat_contract(case, buf, what="C"):
+    nan = torch.isnan(buf.float())
+    n = buf.numel() - 128
+    bad_out = int((~nan[:64]).sum() + (~nan[64 + n:]).sum())
+    assert bad_out == 0, f"{case}: {bad_out} elements outside the contiguous {what} were written"
+    assert not bool(nan[64:64 + n].any()), f"{case}: {int(nan[64:64 + n].sum())} elements of {what} are NaN (unwritten, or read from the poisoned " \
+                                           f"padding), first at flat index {int(nan[64:64 + n].nonzero()[0])}"
+
+
 # ---------------------------------------------------------------- NT cases
 @dataclass
 class NT:
@@ -293,6 +314,8 @@ class NT:
     hd: int = 64
     L: int = 0               # q/k epilogue: rows per sequence (table positions row % L); 0: M
     seed: int = 0
+    layout: str = "fenced"   # fenced: operands and output inside wider NaN buffers (below); model: contiguous, lda = ldw = K and ldc = N,
+                             # 64 NaN elements either side of each (what LatentModel passes; epilogues none and silu)
 
     @property
     def n_rope(self):
@@ -301,12 +324,17 @@ class NT:
     @property
     def id(self):
         ex = ("-acc" if self.acc else "") + ("" if self.bias else "-nobias") + (f"-hd{self.hd}" if self.n_rope else "")
+        ex += "" if self.layout == "fenced" else "-" + self.layout
         return f"{self.T}-{self.epi}-{self.fam}{ex}-{self.M}x{self.N}x{self.K}"
+
+    @property
+    def ldc(self):
+        return ldc_of(self.N) if self.layout == "fenced" else self.N
 
     def path(self, th=GPU_TH):
         if self.epi.startswith("qkrope-split"):
             return split_path(self.T, self.M, self.N, self.K, self.hd, self.n_rope, self.epi.endswith("f16"), th)
-        return nt_path(self.T, self.M, self.N, self.K, self.epi, self.acc, ldc_of(self.N), self.hd, self.n_rope, th=th)
+        return nt_path(self.T, self.M, self.N, self.K, self.epi, self.acc, self.ldc, self.hd, self.n_rope, th=th)
 
 
 def ldc_of(N):
@@ -318,9 +346,14 @@ def run_nt(c: NT, device, twice=False):
     tt = TORCH[T]
     out_t = "bf16" if T == "bf16" else "fp32"
     A32, W32, b, c0, ra, rw = make_nt_inputs(c.fam, M, N, K, device, c.bias and c.fam not in ("range", "cancel", "lo_matters"), c.acc, c.seed)
+    model = c.layout == "model"
+    assert c.layout in ("fenced", "model") and not (model and (T == "x3w" or c.n_rope))
     lda, ldw = cdiv(K + 8, 8) * 8 + 8, cdiv(K + 8, 8) * 8 + 16
-    _, A = poisoned(A32.to(tt), M + 5, lda)
-    if T == "x3w":
+    _, A = flat_buffer((M, K), tt, device, A32.to(tt)) if model else poisoned(A32.to(tt), M + 5, lda)
+    if model:
+        _, W = flat_buffer((N, K), tt, device, W32.to(tt))
+        Wr = W
+    elif T == "x3w":
         st = torch.zeros(N + 3, cdiv(K, 32) * 32 + 32, device=device)
         ops.pack_weight(W32, ops.SplitWeight(st))                    # per 32-element k slab: 32 bf16 high halves, then 32 low halves
         st[N:, :] = NAN
@@ -338,11 +371,13 @@ def run_nt(c: NT, device, twice=False):
     bd = b.double() if b is not None else None
 
     def launch():
-        ldc = ldc_of(N)
-        buf = torch.full((M + 3, ldc), NAN, dtype=tt, device=device)
-        C = buf[:M, 8:8 + N]
-        if c0 is not None:
-            C.copy_(c0)
+        if model:
+            buf, C = flat_buffer((M, N), tt, device, c0)
+        else:
+            buf = torch.full((M + 3, c.ldc), NAN, dtype=tt, device=device)
+            C = buf[:M, 8:8 + N]
+            if c0 is not None:
+                C.copy_(c0)
         if c.epi in ("none", "silu"):
             ops.gemm_nt(A, W, b, C, epilogue=ops.OD_EPI_SILU if c.epi == "silu" else ops.OD_EPI_NONE, accumulate=c.acc, x3=x3)
             return buf, C, None, None
@@ -364,9 +399,12 @@ def run_nt(c: NT, device, twice=False):
         tab = torch.zeros(L, c.hd // 2, 2, device=device)
         ops.rope_table(tab, L, c.hd)
     buf, C, qbuf, qk = launch()
-    p = c.path()
+    p = c.path(GPU_TH if device.type == "cuda" else EMU_TH)        # the backend's own thresholds: its kernel's tile, its row in the label
     case = f"{c.id} [{p.row}]"
-    assert_contract(case, buf, 0, 8, M, N)
+    if model:
+        assert_flat_contract(case, buf)
+    else:
+        assert_contract(case, buf, 0, 8, M, N)
     tr, tc = p.tile
     pre = prod + bd if bd is not None else prod
 
@@ -406,6 +444,7 @@ def run_nt(c: NT, device, twice=False):
                 r, col = (int(i) for i in bad.nonzero()[0])
                 raise AssertionError(f"{case}: {int(bad.sum())} elements differ from the exact product, first ({r}, {col}) = {float(out[r, col])}"
                                      f" against {float(ref[r, col])}, tile {(r // tr, col // tc)}")
+            measured(case, "C (exact)", out, 0.0, 0.0)
         else:
             check_tiles(case, "C", out, ref, tr, tc, nt_bound(T, K, out_t, silu=True))
     elif c.fam == "silu_extreme":
@@ -443,8 +482,14 @@ def qk_reference(pre, tab, wq, wk, L, H, hd):
     return torch.cat(outs, 1)
 
 
+def measured(case, what, out, err, bound):
+    """One line per check for the summaries of a run (pytest -s, or the captured output of a failure): `case` ends in its dispatch row."""
+    print(f"MEASURED {case} {what} {'hip' if out.device.type == 'cuda' else 'emu'} {err:.3e} {bound:.3e}")
+
+
 def check_tiles(case, what, out, ref, tr, tc, bound, scale=None):
     blk, glob, where = tile_rel_l2(out, ref, tr, tc, scale=scale)
+    measured(case, what, out, blk, bound[0])
     assert blk <= bound[0] and glob <= bound[1], f"{case} {what}: tile {blk:.3e} at (tile row, tile column) {where} of {tr} x {tc}, global " \
                                                  f"{glob:.3e}, bounds ({bound[0]:.3e}, {bound[1]:.3e})"
 
@@ -567,10 +612,13 @@ class TN:
     blk: int = 0             # od_gemm_tn_blocks: columns of G in blocks of `blk`, the first `valid` live
     valid: int = 0
     bias: bool = True
+    ldg: int = 0             # both 0: G and A as column sub-views of wider NaN buffers (below).  Otherwise the layout LatentModel passes:
+    lda: int = 0             # contiguous G (M, ldg >= N) and A (M, lda >= K), NaN in columns N..ldg and K..lda, 64 NaN elements either side
 
     @property
     def id(self):
-        return f"{self.T}-{self.fam}{'-det' if self.det else ''}{f'-blk{self.blk}v{self.valid}' if self.blk else ''}-{self.M}x{self.N}x{self.K}"
+        ex = f"-ldg{self.ldg}-lda{self.lda}" if self.ldg else ""
+        return f"{self.T}-{self.fam}{'-det' if self.det else ''}{f'-blk{self.blk}v{self.valid}' if self.blk else ''}{ex}-{self.M}x{self.N}x{self.K}"
 
     def path(self, th=GPU_TH):
         return tn_path(self.T, self.M, self.N, self.K, th)
@@ -603,9 +651,17 @@ def run_tn(c: TN, device, twice=False):
     else:
         G32, A32 = torch.randn(M, N, generator=g, device=device), torch.randn(M, K, generator=g, device=device)
         dW0 = torch.randn(N, K, generator=g, device=device)
-    ldg, lda = cdiv(N, 8) * 8 + 24, cdiv(K, 8) * 8 + 16
-    _, G = poisoned(G32.to(tt), M + 3, ldg, 0, 8)             # column sub-views of wider NaN buffers (16-byte aligned)
-    _, A = poisoned(A32.to(tt), M + 5, lda, 0, 8)
+    if c.ldg or c.lda:
+        assert c.ldg >= N and c.lda >= K
+        _, Gf = flat_buffer((M, c.ldg), tt, device)
+        _, Af = flat_buffer((M, c.lda), tt, device)
+        G, A = Gf[:, :N], Af[:, :K]
+        G.copy_(G32)
+        A.copy_(A32)
+    else:
+        ldg, lda = cdiv(N, 8) * 8 + 24, cdiv(K, 8) * 8 + 16
+        _, G = poisoned(G32.to(tt), M + 3, ldg, 0, 8)             # column sub-views of wider NaN buffers (16-byte aligned)
+        _, A = poisoned(A32.to(tt), M + 5, lda, 0, 8)
     Gd, Ad = G.double(), A.double()
     if c.blk:
         live = torch.tensor([n for n in range(N) if n % c.blk < c.valid], device=device)
@@ -628,7 +684,7 @@ def run_tn(c: TN, device, twice=False):
         return flat, dW, bflat, db
 
     flat, dW, bflat, db = launch()
-    p = c.path()
+    p = c.path(GPU_TH if device.type == "cuda" else EMU_TH)        # the backend's own thresholds: its kernel's tile, its row in the label
     case = f"{c.id} [{p.row}]"
     assert not bool(torch.isnan(dW).any()) and bool(torch.isnan(flat[:64]).all() & torch.isnan(flat[64 + rows * K:]).all()), f"{case}: dW contract"
     assert not bool(torch.isnan(db).any()) and bool(torch.isnan(bflat[:64]).all() & torch.isnan(bflat[64 + rows:]).all()), f"{case}: dbias contract"
@@ -639,6 +695,7 @@ def run_tn(c: TN, device, twice=False):
         bad = dW.double() != ref
         assert not bool(bad.any()), f"{case}: {int(bad.sum())} elements of dW differ from the exact sum, first {tuple(int(i) for i in bad.nonzero()[0])}"
         assert torch.equal(db.double(), refb), f"{case}: dbias differs from the exact column sums"
+        measured(case, "dW, dbias (exact)", dW, 0.0, 0.0)
     else:
         check_tiles(case, "dW", dW.double(), ref, *p.tile, tn_bound(M))
         check_tiles(case, "dbias", db.double()[None, :], refb[None, :], 1, p.tile[0], tn_bound(M))
