@@ -31,8 +31,17 @@ and `h` of `audio_encoder` (summed over the decoder rows when one audio row serv
 end up to its SiLU stays fp32 on the grad path, so in bf16 the training forward is not bit for bit the no-grad forward of the same
 model: the two differ by the bf16 rounding of that front end); `lengths=` and `f32_matmul = "bf16x3"` raise NotImplementedError with grad; `decode` stays no-grad.  Packed GEMM operands follow the parameters'
 version counters, so an optimizer's in-place step needs no `invalidate()`.  A graph is backpropagated once: a second backward through the
-same forward (retain_graph) raises, because the parameter gradients of a call are sums the kernels add into.  `LatentTrainer` / `fit-latent` (loss and MMD kernels,
-parameter arena, fused optimizer, graph capture) are not built.
+same forward (retain_graph) raises, because the parameter gradients of a call are sums the kernels add into.
+
+One forward.  The launch sequence of the layer, the two encoders, both heads, the decoder and the label predictor is written once here
+(`_layer`, `_encoder`, `_audio_fwd`, `_chart_fwd`, `_decode_fwd`, `_label_predictor`) and runs with and without grad; latent_grad.py holds
+only the backward.  What differs is where a buffer comes from, and that is the storage policy the forward is handed:
+  `_Slots`  (no grad) named slots of a shape-keyed workspace, zero-filled when created and shared by a layer's blocks; the residual and
+            the mixer write over their input (so the style head works on a copy of h); nothing is kept; `lengths=` and bf16x3 run here
+  `_Tape`   (grad) a fresh tensor per request, the residual and the mixer write to a new one, and each block's tensors, the resampled
+            streams and the heads' inputs are kept for the backward; SpecFeatures up to its SiLU is fp32 on the parameter itself, cast
+            afterwards; a caller's own skip that would be read in place is cloned; `lengths=` and bf16x3 are refused
+Tensors that outlive a call (skips, h, z, s, logits / chart, labels) are fresh allocations under both.
 """
 from __future__ import annotations
 
@@ -144,6 +153,32 @@ def _shapes(emb_dim: int, style_dim: int, n_downs: int, stride: int, a: LatentMo
     conv("label_predictor.0", (D, style_dim))
     conv("label_predictor.2", (NUM_LABELS, D))
     return s
+
+
+class _Slots:
+    """Storage of a no-grad forward: every buffer is a named slot of one of the model's workspaces (zero-filled when created), so a
+    layer's blocks share their six buffers; the residual and the mixer write over their input; nothing is kept.  Its counterpart with
+    grad is latent_grad's `_Tape`."""
+    fp32_front = False                      # SpecFeatures runs in the compute dtype, on the packed operand
+
+    def __init__(self, ws: Workspace):
+        self.buf = self.zeros = ws.get      # (name, shape, dtype)
+
+    def over(self, x: torch.Tensor) -> torch.Tensor:
+        """Where a kernel that may update x in place writes."""
+        return x
+
+    def fork(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        """What a layer may consume while x is still needed: a copy, because the layer updates its input in place."""
+        t = self.buf(name, x.shape, x.dtype)
+        t.copy_(x)
+        return t
+
+    def skip(self, i: int, sk: torch.Tensor, skf: torch.Tensor) -> torch.Tensor:
+        return skf
+
+    def record(self, **kept):
+        pass
 
 
 class LatentModel(nn.Module):
@@ -307,49 +342,185 @@ class LatentModel(nn.Module):
         """Frame-0 lengths (multiples of chunk_size) of B rows -> (n_downs + 1, B) device int32: row i = the lengths at level i."""
         return self._dev_i32([[x // self.stride ** i for x in lengths] for i in range(self.n_downs + 1)], dev)
 
-    # ------------------------------------------------------------------ unet.py:21-53 (layer)
-    def _layer(self, ws: Workspace, tag: str, p: str, x: torch.Tensor, cond: Optional[torch.Tensor], B: int, L: int,
-               out: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B*L][D] is updated in place by the blocks; returns out_norm(x) in `out` (or a workspace buffer).
-        `lens` (device int32 [B]): row b is valid for frames < lens[b]; the depthwise convs stop there and the returned out_norm is 0 past it
-        (everything else in a block is row-wise, so padded frames only ever affect themselves)."""
-        M, D, dt, x3 = B * L, self.a_dim, x.dtype, self._x3()
-        h = ws.get(tag + ".h", (M, D), dt)
-        hd = ws.get(tag + ".hd", (M, D), dt)
-        vg = ws.get(tag + ".vg", (M, 2 * self.hp), dt)
-        hh = ws.get(tag + ".hh", (M, self.hp), dt)
-        fo = ws.get(tag + ".fo", (M, D), dt)
-        inv = ws.get(tag + ".inv", (M,), torch.float32)
-        k = 1 + 2 * self.args.ae_args.radius
-        for i in range(self.args.ae_args.n_layers):
-            ssg = None
-            if cond is not None:
-                ssg = ws.get(f"{tag}.ssg{i}", (B, 3 * D), torch.float32)
-                ops.linear_small(cond, self.P(f"{p}films.{i}.weight"), self.P(f"{p}films.{i}.bias"), ssg)
-            b = f"{p}blocks.{i}.0."
-            ops.rmsnorm_affine_film(x, self.P(f"{p}norms.{i}.gamma"), ssg, h, B, L)
-            if lens is None:
-                ops.dwconv(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, B, L, k)
-            else:
-                ops.dwconv_varlen(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, lens, B, L, k)
-            ops.gemm_nt(hd, self._packed[b + "proj_vg.1"], self._packed[b + "proj_vg.1.b"], vg, x3=x3)
-            ops.swiglu_rmsnorm(vg, hh, inv, self.hf, self.hp)
-            ops.gemm_nt(hh, self._packed[b + "proj_o"], self.P(b + "proj_o.bias"), fo, x3=x3)
-            ops.rmsnorm_affine_gate_residual(x, fo, self.P(f"{p}blocks.{i}.1.gamma"), ssg, x, B, L)
-        if out is None:
-            out = ws.get(tag + ".out", (M, D), dt)
-        if lens is None:
-            ops.rmsnorm_affine_film(x, self.P(p + "out_norm.gamma"), None, out, B, L)
-        else:
-            ops.rmsnorm_affine_film_varlen(x, self.P(p + "out_norm.gamma"), None, out, lens, B, L)
-        return out
-
-    # ------------------------------------------------------------------ latent/model.py:54 (audio_encoder)
     def _grad_path(self, *inputs) -> bool:
         """Gradients are wanted: grad mode is on and a parameter (`model.requires_grad_(True)`) or one of `inputs` requires grad."""
         return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in inputs) or
                                             any(p.requires_grad for p in self._params()))
 
+    # ------------------------------------------------------------------ the forward.  `st` is the storage policy (_Slots, or latent_grad's
+    # _Tape); `lv` / `lens` are the device lengths of `lengths=` per level (None: dense); operands are packed by the caller (`_pack`).
+    def _layer(self, st, tag: str, p: str, x: torch.Tensor, cond: Optional[torch.Tensor], B: int, L: int,
+               outlive: bool = False, lens: Optional[torch.Tensor] = None):
+        """unet.py:21-53.  x [B*L][D] through the blocks, then out_norm(x) into a buffer of `st` (`outlive`: into a tensor of its own, for
+        the caller to hand on); returns it and the record `_Tape.layer_bwd` reads.  `lens` (device int32 [B]): row b is valid for frames < lens[b]; the depthwise convs stop there and the
+        returned out_norm is 0 past it (everything else in a block is row-wise, so padded frames only ever affect themselves)."""
+        M, D, dt, x3, pk = B * L, self.a_dim, x.dtype, self._x3(), self._packed
+        k = 1 + 2 * self.args.ae_args.radius
+        blocks = []
+        for i in range(self.args.ae_args.n_layers):
+            ssg = None
+            if cond is not None:
+                ssg = st.buf(f"{tag}.ssg{i}", (B, 3 * D), torch.float32)
+                ops.linear_small(cond, self.P(f"{p}films.{i}.weight"), self.P(f"{p}films.{i}.bias"), ssg)
+            b = f"{p}blocks.{i}.0."
+            h = st.buf(tag + ".h", (M, D), dt)
+            hd = st.buf(tag + ".hd", (M, D), dt)
+            vg = st.buf(tag + ".vg", (M, 2 * self.hp), dt)
+            hh = st.buf(tag + ".hh", (M, self.hp), dt)
+            fo = st.buf(tag + ".fo", (M, D), dt)
+            xo = st.over(x)
+            inv = st.buf(tag + ".inv", (M,), torch.float32)
+            ops.rmsnorm_affine_film(x, self.P(f"{p}norms.{i}.gamma"), ssg, h, B, L)
+            ops.dwconv(h, self.P(b + "proj_vg.0.weight"), self.P(b + "proj_vg.0.bias"), hd, B, L, k, lens)
+            ops.gemm_nt(hd, pk[b + "proj_vg.1"], pk[b + "proj_vg.1.b"], vg, x3=x3)
+            ops.swiglu_rmsnorm(vg, hh, inv, self.hf, self.hp)
+            ops.gemm_nt(hh, pk[b + "proj_o"], self.P(b + "proj_o.bias"), fo, x3=x3)
+            ops.rmsnorm_affine_gate_residual(x, fo, self.P(f"{p}blocks.{i}.1.gamma"), ssg, xo, B, L)
+            blocks.append((x, ssg, h, hd, vg, hh, inv, fo))
+            x = xo
+        out = torch.empty(M, D, dtype=dt, device=x.device) if outlive else st.buf(tag + ".out", (M, D), dt)
+        ops.rmsnorm_affine_film(x, self.P(p + "out_norm.gamma"), None, out, B, L, lens=lens)
+        return out, (p, blocks, x, cond, B, L)
+
+    def _encoder(self, st, p: str, x: torch.Tensor, B: int, L: int, lv, outlive: bool):
+        """unet.py:55-82.  Per level a layer, then the strided conv down: returns [(the layer's record, its output, Lo)], the last x and
+        its frames per row.  `outlive`: the outputs and the last x are handed to the caller (audio_encoder's skips and h), so each is a
+        tensor of its own, not a buffer of `st`."""
+        D, dt, levels = self.a_dim, x.dtype, []
+        for i in range(self.n_downs):
+            y, rec = self._layer(st, f"l{i}", f"{p}layers.{i}.", x, None, B, L, outlive, lv[i])
+            Lo = L // self.stride
+            x = (torch.empty(B * Lo, D, dtype=dt, device=x.device) if outlive and i == self.n_downs - 1
+                 else st.buf(f"x{i + 1}", (B * Lo, D), dt))
+            ops.unet_down(y, self.P(f"{p}downs.{i}.0.weight"), self.P(f"{p}downs.{i}.0.bias"), x, B, Lo, self.stride, lv[i])
+            levels.append((rec, y, Lo))
+            L = Lo
+        return levels, x, L
+
+    def _head(self, x: torch.Tensor, name: str, B: int, L: int, n_sigmoid: int, rms: bool, lens) -> torch.Tensor:
+        """x [B*L][D] -> (B, N, L) fp32 through the 1x1 conv `name`: sigmoid on the first n_sigmoid channels, or rms_norm over all."""
+        W = self.P(name + ".weight")
+        out = torch.empty(B, W.shape[0], L, dtype=torch.float32, device=x.device)
+        ops.chart_head(x, W.view(W.shape[0], -1), self.P(name + ".bias"), out, B, L, n_sigmoid, rms=rms, lens=lens)
+        return out
+
+    def _audio_fwd(self, st, audio: torch.Tensor, lv=None):
+        """latent/model.py:54.  audio (Ba, 72, L) fp32, contiguous -> the skips and h as (Ba, D, L_i) views of frame-major tensors of
+        their own (they outlive the call)."""
+        Ba, _, L = audio.shape
+        dt, D, x3 = self._dtype(), self.a_dim, self._x3()
+        lv = [None] * (self.n_downs + 1) if lv is None else lv
+        # st.fp32_front: SpecFeatures stays fp32 in both modes, its 96 -> D projection included (the fp32 parameter is the GEMM operand): its
+        # eight- and 32-element gradients are sums over every frame, where a rounded operand's error does not average out
+        fdt = torch.float32 if st.fp32_front else dt
+        p = "audio_encoder.0.net."
+        f96 = st.buf("f96", (Ba * L, 32 * (A_DIM // 24)), fdt)
+        ops.spec_features_conv(audio, *(self.P(p + n) for n in ("1.weight", "1.bias", "2.gamma", "4.weight", "4.bias", "5.gamma")), f96,
+                               lens=lv[0])
+        pre = st.buf("pre", (Ba * L, D), fdt)
+        w8 = self.P(p + "8.weight").view(D, -1) if st.fp32_front else self._packed["audio_encoder.0.net.8"]
+        ops.gemm_nt(f96, w8, self.P(p + "8.bias"), pre, x3=x3)
+        x = st.buf("x0", (Ba * L, D), fdt)
+        ops.rmsnorm_affine_film(pre, self.P(p + "9.gamma"), None, x, Ba, L, act=OD_ACT_SILU)
+        if fdt != dt:
+            x32, x = x, st.buf("x0c", (Ba * L, D), dt)
+            ops.cast_rows(x32, x)
+        levels, x, _ = self._encoder(st, "audio_encoder.1.", x, Ba, L, lv, outlive=True)
+        st.record(audio=audio, Ba=Ba, L=L, f96=f96, pre=pre, levels=levels)
+        return [skip.view(Ba, -1, D).permute(0, 2, 1) for _, skip, _ in levels], x.view(Ba, -1, D).permute(0, 2, 1)
+
+    def _chart_fwd(self, st, chart: torch.Tensor, lv=None):
+        """latent/model.py:93-101.  chart (B, 9, L) fp32, contiguous -> z (B, emb_dim, L / chunk_size), s (B, style_dim): chart encoder,
+        style head (layer + AttnPool + rms_norm), temporal layer / head."""
+        B, _, L = chart.shape
+        dt, D, x3, pk = self._dtype(), self.a_dim, self._x3(), self._packed
+        lv = [None] * (self.n_downs + 1) if lv is None else lv
+        cf = self._frames(chart, dt, st.zeros("cf", (B * L, 16), dt))      # columns 9..15 stay zero
+        x = st.buf("x0", (B * L, D), dt)
+        ops.gemm_nt(cf, pk["chart_encoder.0"], self.P("chart_encoder.0.bias"), x, x3=x3)
+        levels, h, Li = self._encoder(st, "chart_encoder.1.", x, B, L, lv, outlive=False)
+        ll = lv[self.n_downs]                                 # h is [B*l][D]; both heads below read it
+        # style head: layer -> AttnPool -> rms_norm (no gain)
+        ys, rec_s = self._layer(st, "sh", "style_head.0.", st.fork("hs", h), None, B, Li, lens=ll)
+        heads, hd = self.args.style_heads, self.args.style_head_dim
+        sc = st.buf("sc", (B * Li, heads), dt)
+        va = st.buf("va", (B * Li, heads * hd), dt)
+        ops.gemm_nt(ys, pk["style_head.1.scores"], self.P("style_head.1.scores.bias"), sc, x3=x3)
+        ops.gemm_nt(ys, pk["style_head.1.values"], self.P("style_head.1.values.bias"), va, x3=x3)
+        pooled = st.buf("pooled", (B, heads * hd), torch.float32)
+        ops.attn_pool(sc, va, pooled, B, Li, heads, hd, ll)
+        s_pre = st.buf("s_pre", (B, self.style_dim), torch.float32)
+        ops.linear_small(pooled, self.P("style_head.1.proj_out.weight"), self.P("style_head.1.proj_out.bias"), s_pre)
+        s = torch.empty(B, self.style_dim, dtype=torch.float32, device=chart.device)
+        ops.rmsnorm_rows(s_pre, None, s, 1e-6)
+        # temporal layer (FiLM from s) -> Conv1d(D -> emb_dim) -> rms_norm over the emb_dim channels
+        yt, rec_t = self._layer(st, "tl", "temporal_layer.", h, s, B, Li, lens=ll)
+        z = self._head(yt, "temporal_head.0", B, Li, 0, True, ll)
+        st.record(B=B, L=L, l=Li, cf=cf, levels=levels, ys=ys, rec_s=rec_s, sc=sc, va=va, pooled=pooled, s_pre=s_pre, s=s, yt=yt, rec_t=rec_t)
+        return z, s
+
+    def _decode_fwd(self, st, z: torch.Tensor, s: torch.Tensor, skips, n_sigmoid: int, lv=None, prow=None, songs: Optional[int] = None):
+        """latent/model.py:103-114.  z (B, E, l), s (B, style_dim) fp32, contiguous -> (B, 9, L) with a sigmoid on the first n_sigmoid
+        channels.  Varlen: skip row prow[b] (device int32 [B]) of `songs` rows serves decoder row b."""
+        skips = list(skips)
+        if len(skips) != self.n_downs:
+            raise ValueError(f"expected {self.n_downs} skips, got {len(skips)}")
+        B, E, l = z.shape
+        dt, D, x3, pk = self._dtype(), self.a_dim, self._x3(), self._packed
+        lv = [None] * (self.n_downs + 1) if lv is None else lv
+        x = st.buf("x0", (B * l, D), dt)
+        ops.proj_in(z, self.P("proj_emb.weight").view(D, E), self.P("proj_emb.bias"), x)
+        ups, Li = [], l
+        for i in range(self.n_downs):
+            Lu = Li * self.stride
+            lvl = self.n_downs - i                                # level of x; xu is at level lvl - 1
+            sk = skips[lvl - 1]
+            Bs = sk.shape[0]
+            if sk.shape[1] != D or sk.shape[2] != Lu or (Bs not in (1, B) if songs is None else Bs != songs):
+                raise ValueError(f"skip {tuple(sk.shape)} does not match ({f'{B}|1' if songs is None else f'G = {songs}'}, {D}, {Lu})")
+            bc = Bs == 1 and B > 1
+            xu = st.buf(f"xu{i}", (B * Lu, D), dt)
+            ops.unet_up(x, self.P(f"decoder.ups.{i}.1.weight"), self.P(f"decoder.ups.{i}.1.bias"), xu, B, Li, self.stride, lv[lvl])
+            skf = st.skip(lvl - 1, sk, self._frames(sk, dt))
+            m = f"decoder.mixers.{i}."
+            pr = st.buf(f"pr{i}", (Bs * Lu, D), dt)
+            ops.gemm_nt(skf, pk[m + "proj.0"], self.P(m + "proj.0.bias"), pr, x3=x3)
+            gx = st.buf(f"gx{i}", (B * Lu, D), dt)
+            ops.gemm_nt(xu, pk[m + "gate"], self.P(m + "gate.bias"), gx, x3=x3)
+            xm = st.over(xu)
+            ops.unet_mixer(xu, pr, bc, gx, self.P(m + "proj.1.gamma"), xm, B, Lu, prow=prow)
+            y, rec = self._layer(st, f"l{i}", f"decoder.layers.{i}.", xm, s, B, Lu, lens=lv[lvl - 1])
+            ups.append((x, xu, skf, pr, gx, bc, Bs, rec, Li))
+            x, Li = y, Lu
+        st.record(z=z, s=s, B=B, l=l, ups=ups, x_out=x, Lout=Li)
+        return self._head(x, "proj_out", B, Li, n_sigmoid, False, lv[0])
+
+    def _label_predictor(self, s: torch.Tensor, tape=None) -> torch.Tensor:
+        """latent/model.py:72-76.  s (B, style_dim) fp32, contiguous.  With a tape the hidden layer's pre-activation is stored too."""
+        B = s.shape[0]
+        hid = torch.empty(B, self.a_dim, dtype=torch.float32, device=s.device)
+        pre = None if tape is None else torch.empty_like(hid)
+        out = torch.empty(B, NUM_LABELS, dtype=torch.float32, device=s.device)
+        ops.linear_small(s, self.P("label_predictor.0.weight"), self.P("label_predictor.0.bias"), hid, pre, OD_ACT_SILU)
+        ops.linear_small(hid, self.P("label_predictor.2.weight"), self.P("label_predictor.2.bias"), out)
+        if tape is not None:
+            tape.record(s=s, hid=hid, hid_pre=pre)
+        return out
+
+    def _frames(self, t: torch.Tensor, dt: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(B, C, L) tensor -> frame-major [B*L][C] of the compute dtype; free for the views audio_encoder returns.  With `out`
+        ([B*L][>= C] of dt) the first C columns of it are written."""
+        B, C, L = t.shape
+        if out is None:
+            fm = t.permute(0, 2, 1)
+            if fm.is_contiguous() and t.dtype == dt:
+                return fm.reshape(B * L, C)
+            out = torch.empty(B * L, C, dtype=dt, device=t.device)
+        ops.cl_to_frames(t.detach().to(torch.float32).contiguous(), out)
+        return out
+
+    # ------------------------------------------------------------------ the calls: checks, then the no-grad forward in the model's
+    # workspaces, or latent_grad's autograd Functions around the same forward
     def _audio_encoder(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None):
         if not self._grad_path():                     # (the spectrogram itself takes no gradient)
             return self._audio_encoder_nograd(audio, lengths)
@@ -370,49 +541,10 @@ class LatentModel(nn.Module):
         if L % self.chunk_size:
             raise ValueError(f"audio length {L} is not a multiple of chunk_size {self.chunk_size} (pad_to_multiple first)")
         lv = None if lengths is None else self._level_lens(self._check_lengths(lengths, Ba, L, "audio_encoder"), audio.device)
-        dt, D, x3 = self._dtype(), self.a_dim, self._x3()
+        dt = self._dtype()
         self._pack(dt)
-        ws = self._workspace("enc", Ba, L, dt)
-        p = "audio_encoder.0.net."
-        f96 = ws.get("f96", (Ba * L, 32 * (A_DIM // 24)), dt)
-        spec_w = (self.P(p + "1.weight"), self.P(p + "1.bias"), self.P(p + "2.gamma"), self.P(p + "4.weight"), self.P(p + "4.bias"),
-                  self.P(p + "5.gamma"))
-        if lv is None:
-            ops.spec_features_conv(audio, *spec_w, f96)
-        else:
-            ops.spec_features_conv_varlen(audio, *spec_w, f96, lv[0])
-        pre = ws.get("pre", (Ba * L, D), dt)
-        ops.gemm_nt(f96, self._packed["audio_encoder.0.net.8"], self.P(p + "8.bias"), pre, x3=x3)
-        x = ws.get("x0", (Ba * L, D), dt)
-        ops.rmsnorm_affine_film(pre, self.P(p + "9.gamma"), None, x, Ba, L, act=OD_ACT_SILU)
-        skips, Li = [], L
-        for i in range(self.n_downs):
-            # the skip outlives this call: it gets its own storage, not a workspace slot
-            skip = torch.empty(Ba * Li, D, dtype=dt, device=audio.device)
-            self._layer(ws, f"l{i}", f"audio_encoder.1.layers.{i}.", x, None, Ba, Li, out=skip, lens=None if lv is None else lv[i])
-            skips.append(skip.view(Ba, Li, D).permute(0, 2, 1))
-            Lo = Li // self.stride
-            x = (torch.empty(Ba * Lo, D, dtype=dt, device=audio.device) if i == self.n_downs - 1
-                 else ws.get(f"x{i + 1}", (Ba * Lo, D), dt))
-            dw = (self.P(f"audio_encoder.1.downs.{i}.0.weight"), self.P(f"audio_encoder.1.downs.{i}.0.bias"))
-            if lv is None:
-                ops.unet_down(skip, *dw, x, Ba, Lo, self.stride)
-            else:
-                ops.unet_down_varlen(skip, *dw, x, lv[i], Ba, Lo, self.stride)
-            Li = Lo
-        return skips, x.view(Ba, Li, D).permute(0, 2, 1)
+        return self._audio_fwd(_Slots(self._workspace("enc", Ba, L, dt)), audio, lv)
 
-    def _frames(self, t: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
-        """(B, C, L) tensor -> frame-major [B*L][C] of the compute dtype; free for the views audio_encoder returns."""
-        B, C, L = t.shape
-        fm = t.permute(0, 2, 1)
-        if fm.is_contiguous() and t.dtype == dt:
-            return fm.reshape(B * L, C)
-        out = torch.empty(B * L, C, dtype=dt, device=t.device)
-        ops.cl_to_frames(t.detach().to(torch.float32).contiguous(), out)
-        return out
-
-    # ------------------------------------------------------------------ latent/model.py:103-114
     @torch.no_grad()
     def _decode(self, z, s, audio, skips, n_sigmoid: int, lengths=None, offs=None):
         if lengths is None and offs is not None:
@@ -424,9 +556,9 @@ class LatentModel(nn.Module):
         z = z.detach().to(torch.float32).contiguous()
         s = s.detach().to(torch.float32).contiguous()
         B, E, l = z.shape
-        dt, D, x3 = self._dtype(), self.a_dim, self._x3()
+        dt = self._dtype()
         self._pack(dt)
-        lv = prow = None
+        lv = prow = G = None
         if lengths is not None:
             # varlen: song g = rows offs[g]:offs[g+1] of z / s, skips[i] row g; lengths[g] in chart frames
             G = len(lengths)
@@ -437,48 +569,8 @@ class LatentModel(nn.Module):
             rows = [g for g in range(G) for _ in range(offs[g + 1] - offs[g])]
             lv = self._level_lens([lengths[g] for g in rows], z.device)
             prow = self._dev_i32(rows, z.device)
-        ws = self._workspace("dec" if lv is None else f"dec.vl{len(lengths)}", B, l, dt)
-        skips = list(skips)
-        if len(skips) != self.n_downs:
-            raise ValueError(f"expected {self.n_downs} skips, got {len(skips)}")
-        x = ws.get("x0", (B * l, D), dt)
-        ops.proj_in(z, self.P("proj_emb.weight").view(D, E), self.P("proj_emb.bias"), x)
-        Li = l
-        for i in range(self.n_downs):
-            Lu = Li * self.stride
-            lvl = self.n_downs - i                                # level of x; xu is at level lvl - 1
-            xu = ws.get(f"xu{i}", (B * Lu, D), dt)
-            uw = (self.P(f"decoder.ups.{i}.1.weight"), self.P(f"decoder.ups.{i}.1.bias"))
-            if lv is None:
-                ops.unet_up(x, *uw, xu, B, Li, self.stride)
-            else:
-                ops.unet_up_varlen(x, *uw, xu, lv[lvl], B, Li, self.stride)
-            sk = skips.pop()
-            Bs = sk.shape[0]
-            if lv is not None:
-                if sk.shape[1] != D or sk.shape[2] != Lu or Bs != len(lengths):
-                    raise ValueError(f"skip {tuple(sk.shape)} does not match (G = {len(lengths)}, {D}, {Lu})")
-            elif sk.shape[1] != D or sk.shape[2] != Lu or Bs not in (1, B):
-                raise ValueError(f"skip {tuple(sk.shape)} does not match ({B}|1, {D}, {Lu})")
-            skf = self._frames(sk, dt)
-            m = f"decoder.mixers.{i}."
-            pr = ws.get(f"pr{i}", (Bs * Lu, D), dt)
-            ops.gemm_nt(skf, self._packed[m + "proj.0"], self.P(m + "proj.0.bias"), pr, x3=x3)
-            gx = ws.get(f"gx{i}", (B * Lu, D), dt)
-            ops.gemm_nt(xu, self._packed[m + "gate"], self.P(m + "gate.bias"), gx, x3=x3)
-            if lv is None:
-                ops.unet_mixer(xu, pr, Bs == 1 and B > 1, gx, self.P(m + "proj.1.gamma"), xu, B, Lu)
-            else:
-                ops.unet_mixer_varlen(xu, pr, prow, gx, self.P(m + "proj.1.gamma"), xu, B, Lu)
-            x = self._layer(ws, f"l{i}", f"decoder.layers.{i}.", xu, s, B, Lu, lens=None if lv is None else lv[lvl - 1])
-            Li = Lu
-        out = torch.empty(B, X_DIM, Li, dtype=torch.float32, device=z.device)
-        hw = (self.P("proj_out.weight").view(X_DIM, D), self.P("proj_out.bias"))
-        if lv is None:
-            ops.chart_head(x, *hw, out, B, Li, n_sigmoid)
-        else:
-            ops.chart_head_varlen(x, *hw, out, lv[0], B, Li, n_sigmoid)
-        return out, s
+        ws = self._workspace("dec" if lv is None else f"dec.vl{G}", B, l, dt)
+        return self._decode_fwd(_Slots(ws), z, s, skips, n_sigmoid, lv, prow, G), s
 
     def decode_logits(self, z, s, *, audio=None, skips=None, lengths=None, offs=None) -> torch.Tensor:
         if not self._grad_path(z, s, *(skips or ())):
@@ -490,14 +582,6 @@ class LatentModel(nn.Module):
                 raise ValueError("decode needs `audio` or `skips`")
             skips, _ = self._audio_encoder(audio)
         return latent_grad.decode_logits(self, z, s, skips)
-
-    def _label_predictor(self, s: torch.Tensor) -> torch.Tensor:            # latent/model.py:72-76
-        B = s.shape[0]
-        hid = torch.empty(B, self.a_dim, dtype=torch.float32, device=s.device)
-        out = torch.empty(B, NUM_LABELS, dtype=torch.float32, device=s.device)
-        ops.linear_small(s, self.P("label_predictor.0.weight"), self.P("label_predictor.0.bias"), hid, None, OD_ACT_SILU)
-        ops.linear_small(hid, self.P("label_predictor.2.weight"), self.P("label_predictor.2.bias"), out)
-        return out
 
     @torch.no_grad()
     def decode(self, z, s, *, audio=None, skips=None, lengths=None, offs=None):
@@ -513,7 +597,6 @@ class LatentModel(nn.Module):
         with torch.no_grad():
             return self.decode_logits(z, s, audio=audio), self._label_predictor(s.detach().to(torch.float32).contiguous())
 
-    # ------------------------------------------------------------------ latent/model.py:93-101 (encode_chart)
     def encode_chart(self, chart: torch.Tensor, lengths: Optional[Sequence[int]] = None):
         if not self._grad_path():                     # (the chart itself takes no gradient)
             return self._encode_chart_nograd(chart, lengths)
@@ -525,10 +608,8 @@ class LatentModel(nn.Module):
 
     @torch.no_grad()
     def _encode_chart_nograd(self, chart: torch.Tensor, lengths: Optional[Sequence[int]] = None):
-        """chart (B, 9, L) -> z (B, emb_dim, L / chunk_size), s (B, style_dim): the dataset-encoding direction
-        (scripts/encode_latents.py): chart encoder, style head (layer + AttnPool + rms_norm), temporal layer / head.
-        `lengths` (one per map, multiples of chunk_size): map b holds lengths[b] frames; z is 0 past lengths[b] / chunk_size and s pools
-        over the map's own frames."""
+        """The dataset-encoding direction (scripts/encode_latents.py).  `lengths` (one per map, multiples of chunk_size): map b holds
+        lengths[b] frames; z is 0 past lengths[b] / chunk_size and s pools over the map's own frames."""
         chart = chart.detach().to(torch.float32).contiguous()
         B, X, L = chart.shape
         if X != X_DIM:
@@ -536,50 +617,7 @@ class LatentModel(nn.Module):
         if L % self.chunk_size:
             raise ValueError(f"chart length {L} is not a multiple of chunk_size {self.chunk_size} (pad_to_multiple first)")
         lv = None if lengths is None else self._level_lens(self._check_lengths(lengths, B, L, "encode_chart"), chart.device)
-        dt, D, x3 = self._dtype(), self.a_dim, self._x3()
+        dt = self._dtype()
         self._pack(dt)
-        ws = self._workspace("chart", B, L, dt)
-        cf = ws.get("cf", (B * L, 16), dt)                   # columns 9..15 stay zero
-        ops.cl_to_frames(chart, cf)
-        x = ws.get("x0", (B * L, D), dt)
-        ops.gemm_nt(cf, self._packed["chart_encoder.0"], self.P("chart_encoder.0.bias"), x, x3=x3)
-        Li = L
-        for i in range(self.n_downs):
-            y = self._layer(ws, f"l{i}", f"chart_encoder.1.layers.{i}.", x, None, B, Li, lens=None if lv is None else lv[i])
-            Lo = Li // self.stride
-            x = ws.get(f"x{i + 1}", (B * Lo, D), dt)
-            dw = (self.P(f"chart_encoder.1.downs.{i}.0.weight"), self.P(f"chart_encoder.1.downs.{i}.0.bias"))
-            if lv is None:
-                ops.unet_down(y, *dw, x, B, Lo, self.stride)
-            else:
-                ops.unet_down_varlen(y, *dw, x, lv[i], B, Lo, self.stride)
-            Li = Lo
-        ll = None if lv is None else lv[self.n_downs]
-        h = x                                                 # [B*l][D]; both heads below read it
-        # style head: layer -> AttnPool -> rms_norm (no gain)
-        hs = ws.get("hs", (B * Li, D), dt)
-        hs.copy_(h)                                           # _layer updates its input in place
-        y = self._layer(ws, "sh", "style_head.0.", hs, None, B, Li, lens=ll)
-        heads, hd = self.args.style_heads, self.args.style_head_dim
-        sc = ws.get("sc", (B * Li, heads), dt)
-        va = ws.get("va", (B * Li, heads * hd), dt)
-        ops.gemm_nt(y, self._packed["style_head.1.scores"], self.P("style_head.1.scores.bias"), sc, x3=x3)
-        ops.gemm_nt(y, self._packed["style_head.1.values"], self.P("style_head.1.values.bias"), va, x3=x3)
-        pooled = ws.get("pooled", (B, heads * hd), torch.float32)
-        if ll is None:
-            ops.attn_pool(sc, va, pooled, B, Li, heads, hd)
-        else:
-            ops.attn_pool_varlen(sc, va, pooled, ll, B, Li, heads, hd)
-        s_pre = ws.get("s_pre", (B, self.style_dim), torch.float32)
-        ops.linear_small(pooled, self.P("style_head.1.proj_out.weight"), self.P("style_head.1.proj_out.bias"), s_pre)
-        s = torch.empty(B, self.style_dim, dtype=torch.float32, device=chart.device)
-        ops.rmsnorm_rows(s_pre, None, s, 1e-6)
-        # temporal layer (FiLM from s) -> Conv1d(D -> emb_dim) -> rms_norm over the emb_dim channels
-        y = self._layer(ws, "tl", "temporal_layer.", h, s, B, Li, lens=ll)
-        z = torch.empty(B, self.emb_dim, Li, dtype=torch.float32, device=chart.device)
-        tw = (self.P("temporal_head.0.weight").view(self.emb_dim, D), self.P("temporal_head.0.bias"))
-        if ll is None:
-            ops.chart_head(y, *tw, z, B, Li, 0, rms=True)
-        else:
-            ops.chart_head_varlen(y, *tw, z, ll, B, Li, 0, rms=True)
-        return z, s
+        return self._chart_fwd(_Slots(self._workspace("chart", B, L, dt)), chart, lv)
+

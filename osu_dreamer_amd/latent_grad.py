@@ -1,11 +1,13 @@
-"""Backpropagation through `LatentModel` on the HIP path: the training forward and the backward of `audio_encoder`, `encode_chart`,
-`decode_logits` and the label predictor, as `torch.autograd.Function`s over the kernels of csrc/latent.hip (reference autograd of
+"""Backpropagation through `LatentModel` on the HIP path: the backward of `audio_encoder`, `encode_chart`, `decode_logits` and the label
+predictor, as `torch.autograd.Function`s over the kernels of csrc/latent.hip (reference autograd of
 osu_dreamer/models/latent/{model,unet,spec_features}.py).
 
-A training forward keeps what its backward reads (each block's input, h, hd, vg, hh, inv_rms, fo and FiLM rows; the resampled streams; the
-heads' inputs) in tensors owned by that call (`_Tape`), never in the model's shape-keyed inference workspaces, so several forwards can be alive at
-once.  Parameters are inputs of the Functions, so autograd fills their `.grad`; parameter gradients are fp32, activations and their
-gradients are of the compute dtype (fp32, or bf16 with fp32 accumulation), except SpecFeatures (audio_encoder.0), which runs in fp32 in both.
+There is one forward, in latent.py: the Functions run it with a `_Tape` as its storage policy where inference runs it with `_Slots`.  The
+tape hands out a fresh tensor per request, has the residual and the mixer write to a new tensor, and keeps what the backward reads (each
+block's input, h, hd, vg, hh, inv_rms, fo and FiLM rows; the resampled streams; the heads' inputs) in tensors owned by that call, never in
+the model's shape-keyed inference workspaces, so several forwards can be alive at once.  Parameters are inputs of the Functions, so
+autograd fills their `.grad`; parameter gradients are fp32, activations and their gradients are of the compute dtype (fp32, or bf16 with
+fp32 accumulation), except SpecFeatures (audio_encoder.0), which runs in fp32 in both.
 """
 from __future__ import annotations
 
@@ -33,7 +35,31 @@ class _Tape:
         # dx) then add into integer shadows of the buffers registered here, folded in by flush() before the first reader
         self.det = det.context(self.dev)
 
-    # ------------------------------------------------------------------ storage
+    # ------------------------------------------------------------------ the forward's storage policy (latent.py's `_Slots` is the other)
+    fp32_front = True                       # SpecFeatures up to its SiLU runs in fp32 on the parameter itself, cast_rows after it
+
+    def buf(self, name: str, shape, dtype) -> torch.Tensor:
+        return torch.empty(shape, dtype=dtype, device=self.dev)
+
+    def zeros(self, name: str, shape, dtype) -> torch.Tensor:
+        return torch.zeros(shape, dtype=dtype, device=self.dev)
+
+    def over(self, x: torch.Tensor) -> torch.Tensor:
+        """Where a kernel that may update x in place writes: the backward reads x, so elsewhere."""
+        return torch.empty_like(x)
+
+    def fork(self, name: str, x: torch.Tensor) -> torch.Tensor:
+        return x                            # (no layer writes over its input here)
+
+    def skip(self, i: int, sk: torch.Tensor, skf: torch.Tensor) -> torch.Tensor:
+        """skf: skip i (sk) as frames.  A caller's tensor, not a training audio_encoder's, read in place: the backward reads it, so keep
+        its values."""
+        return skf.clone() if self.own_skip[i] and skf.data_ptr() == sk.data_ptr() else skf
+
+    def record(self, **kept):
+        self.__dict__.update(kept)
+
+    # ------------------------------------------------------------------ the backward's storage
     def E(self, rows: int, cols: int, dtype=None) -> torch.Tensor:
         return torch.empty(rows, cols, dtype=dtype or self.dt, device=self.dev)
 
@@ -86,32 +112,6 @@ class _Tape:
         B, C, L = t.shape
         return t.to(self.dt).permute(0, 2, 1).contiguous().reshape(B * L, C)
 
-    # ------------------------------------------------------------------ unet.py:39-53 (layer)
-    def layer_fwd(self, p: str, x: torch.Tensor, cond: Optional[torch.Tensor], B: int, L: int):
-        m, pk = self.m, self.pk
-        M, D, hf, hp = B * L, m.a_dim, m.hf, m.hp
-        k = 1 + 2 * m.args.ae_args.radius
-        blocks = []
-        for i in range(m.args.ae_args.n_layers):
-            ssg = None
-            if cond is not None:
-                ssg = torch.empty(B, 3 * D, dtype=F32, device=self.dev)
-                ops.linear_small(cond, m.P(f"{p}films.{i}.weight"), m.P(f"{p}films.{i}.bias"), ssg)
-            b = f"{p}blocks.{i}.0."
-            h, hd, vg, hh, fo, xo = self.E(M, D), self.E(M, D), self.E(M, 2 * hp), self.E(M, hp), self.E(M, D), self.E(M, D)
-            inv = torch.empty(M, dtype=F32, device=self.dev)
-            ops.rmsnorm_affine_film(x, m.P(f"{p}norms.{i}.gamma"), ssg, h, B, L)
-            ops.dwconv(h, m.P(b + "proj_vg.0.weight"), m.P(b + "proj_vg.0.bias"), hd, B, L, k)
-            ops.gemm_nt(hd, pk[b + "proj_vg.1"], pk[b + "proj_vg.1.b"], vg)
-            ops.swiglu_rmsnorm(vg, hh, inv, hf, hp)
-            ops.gemm_nt(hh, pk[b + "proj_o"], m.P(b + "proj_o.bias"), fo)
-            ops.rmsnorm_affine_gate_residual(x, fo, m.P(f"{p}blocks.{i}.1.gamma"), ssg, xo, B, L)
-            blocks.append((x, ssg, h, hd, vg, hh, inv, fo))
-            x = xo
-        out = self.E(M, D)
-        ops.rmsnorm_affine_film(x, m.P(p + "out_norm.gamma"), None, out, B, L)
-        return out, (p, blocks, x, cond, B, L)
-
     def layer_bwd(self, rec, dout: torch.Tensor, dcond: Optional[torch.Tensor]) -> torch.Tensor:
         """dout: the gradient of the layer's output.  Returns the gradient of its input; dcond (B, cond_dim) fp32 += through the films."""
         m, pk, g = self.m, self.pk, self.g
@@ -149,32 +149,6 @@ class _Tape:
         ops.unet_down_bwd(x, m.P(name + ".weight"), dy, dx, self.g(name + ".weight"), self.g(name + ".bias"), ws, B, Lo, m.stride)
         return dx
 
-    # ------------------------------------------------------------------ latent/model.py:54 (audio_encoder)
-    def audio_fwd(self, audio: torch.Tensor):
-        m, pk = self.m, self.pk
-        Ba, _, L = audio.shape
-        D, p = m.a_dim, "audio_encoder.0.net."
-        self.audio, self.Ba, self.L = audio, Ba, L
-        # SpecFeatures stays fp32 in both modes, its 96 -> D projection included (the fp32 parameter is the GEMM operand): its eight- and
-        # 32-element gradients are sums over every frame, where a rounded operand's error does not average out
-        self.f96, self.pre, x = self.E(Ba * L, 96, F32), self.E(Ba * L, D, F32), self.E(Ba * L, D, F32)
-        ops.spec_features_conv(audio, *(m.P(p + k) for k in ("1.weight", "1.bias", "2.gamma", "4.weight", "4.bias", "5.gamma")), self.f96)
-        ops.gemm_nt(self.f96, m.P(p + "8.weight").view(D, 96), m.P(p + "8.bias"), self.pre)
-        ops.rmsnorm_affine_film(self.pre, m.P(p + "9.gamma"), None, x, Ba, L, act=OD_ACT_SILU)
-        if self.dt != F32:
-            x32, x = x, self.E(Ba * L, D)
-            ops.cast_rows(x32, x)
-        self.levels, skips, Li = [], [], L
-        for i in range(m.n_downs):
-            skip, rec = self.layer_fwd(f"audio_encoder.1.layers.{i}.", x, None, Ba, Li)
-            Lo = Li // m.stride
-            x = self.E(Ba * Lo, D)
-            ops.unet_down(skip, m.P(f"audio_encoder.1.downs.{i}.0.weight"), m.P(f"audio_encoder.1.downs.{i}.0.bias"), x, Ba, Lo, m.stride)
-            self.levels.append((rec, skip, Lo))
-            skips.append(skip.view(Ba, Li, D).permute(0, 2, 1))
-            Li = Lo
-        return skips, x.view(Ba, Li, D).permute(0, 2, 1)
-
     def audio_bwd(self, dskips, dh):
         m, pk, g = self.m, self.pk, self.g
         Ba, L, D, p = self.Ba, self.L, m.a_dim, "audio_encoder.0.net."
@@ -203,42 +177,6 @@ class _Tape:
         ops.spec_features_conv_bwd(self.audio, *(m.P(p + k) for k in names), df, *(g(p + k) for k in names),
                                    self.ws(ops.latent_bwd_ws_floats("spec", Ba, L, 0)))
 
-    # ------------------------------------------------------------------ latent/model.py:91-101 (encode_chart)
-    def chart_fwd(self, chart: torch.Tensor):
-        m, pk = self.m, self.pk
-        B, _, L = chart.shape
-        D = m.a_dim
-        self.B, self.L = B, L
-        self.cf = torch.zeros(B * L, 16, dtype=self.dt, device=self.dev)       # columns 9..15 stay zero
-        ops.cl_to_frames(chart, self.cf)
-        x = self.E(B * L, D)
-        ops.gemm_nt(self.cf, pk["chart_encoder.0"], m.P("chart_encoder.0.bias"), x)
-        self.levels, Li = [], L
-        for i in range(m.n_downs):
-            y, rec = self.layer_fwd(f"chart_encoder.1.layers.{i}.", x, None, B, Li)
-            Lo = Li // m.stride
-            x = self.E(B * Lo, D)
-            ops.unet_down(y, m.P(f"chart_encoder.1.downs.{i}.0.weight"), m.P(f"chart_encoder.1.downs.{i}.0.bias"), x, B, Lo, m.stride)
-            self.levels.append((rec, y, Lo))
-            Li = Lo
-        self.l, h = Li, x
-        heads, hd = m.args.style_heads, m.args.style_head_dim
-        self.hpad = (heads + 7) // 8 * 8
-        self.ys, self.rec_s = self.layer_fwd("style_head.0.", h, None, B, Li)
-        self.sc, self.va = self.E(B * Li, heads), self.E(B * Li, heads * hd)
-        ops.gemm_nt(self.ys, pk["style_head.1.scores"], m.P("style_head.1.scores.bias"), self.sc)
-        ops.gemm_nt(self.ys, pk["style_head.1.values"], m.P("style_head.1.values.bias"), self.va)
-        self.pooled = torch.empty(B, heads * hd, dtype=F32, device=self.dev)
-        ops.attn_pool(self.sc, self.va, self.pooled, B, Li, heads, hd)
-        self.s_pre = torch.empty(B, m.style_dim, dtype=F32, device=self.dev)
-        ops.linear_small(self.pooled, m.P("style_head.1.proj_out.weight"), m.P("style_head.1.proj_out.bias"), self.s_pre)
-        self.s = torch.empty(B, m.style_dim, dtype=F32, device=self.dev)
-        ops.rmsnorm_rows(self.s_pre, None, self.s, 1e-6)
-        self.yt, self.rec_t = self.layer_fwd("temporal_layer.", h, self.s, B, Li)
-        z = torch.empty(B, m.emb_dim, Li, dtype=F32, device=self.dev)
-        ops.chart_head(self.yt, m.P("temporal_head.0.weight").view(m.emb_dim, D), m.P("temporal_head.0.bias"), z, B, Li, 0, rms=True)
-        return z, self.s
-
     def chart_bwd(self, dz, ds_out):
         m, pk, g = self.m, self.pk, self.g
         B, l, D = self.B, self.l, m.a_dim
@@ -260,7 +198,7 @@ class _Tape:
         ops.linear_small_bwd(self.pooled, m.P("style_head.1.proj_out.weight"), None, ds_pre, torch.empty_like(ds_pre),
                              g("style_head.1.proj_out.weight"), g("style_head.1.proj_out.bias"), dpooled, False)
         # the score gradients sit in a zero-padded 8-column block: the GEMMs read whole 16-byte chunks
-        dsc, dva, dys = torch.zeros(B * l, self.hpad, dtype=self.dt, device=self.dev), self.E(B * l, heads * hd), self.E(B * l, D)
+        dsc, dva, dys = torch.zeros(B * l, (heads + 7) // 8 * 8, dtype=self.dt, device=self.dev), self.E(B * l, heads * hd), self.E(B * l, D)
         ops.attn_pool_bwd(self.sc, self.va, self.flush(dpooled), dsc, dva, B, l, heads, hd)
         ops.gemm_tn(dsc, self.ys, g("style_head.1.scores.weight"), n_cols=heads, dbias=g("style_head.1.scores.bias"))
         ops.gemm_tn(dva, self.ys, g("style_head.1.values.weight"), dbias=g("style_head.1.values.bias"))
@@ -276,39 +214,6 @@ class _Tape:
         dw16 = self.atomic(torch.zeros(D, 16, dtype=F32, device=self.dev))     # the padded operand's 16 columns; the 9 live ones are the weight's
         ops.gemm_tn(dx, self.cf, dw16, dbias=g("chart_encoder.0.bias"))
         g("chart_encoder.0.weight").view(D, -1).copy_(self.flush(dw16)[:, :m.P("chart_encoder.0.weight").shape[1]])
-
-    # ------------------------------------------------------------------ latent/model.py:103-114 (decode_logits)
-    def decode_fwd(self, z: torch.Tensor, s: torch.Tensor, skips: List[torch.Tensor]):
-        m, pk = self.m, self.pk
-        B, E, l = z.shape
-        D = m.a_dim
-        self.z, self.s, self.B, self.l = z, s, B, l
-        x = self.E(B * l, D)
-        ops.proj_in(z, m.P("proj_emb.weight").view(D, E), m.P("proj_emb.bias"), x)
-        self.ups, Li = [], l
-        for i in range(m.n_downs):
-            Lu = Li * m.stride
-            sk = skips[m.n_downs - 1 - i]
-            Bs = sk.shape[0]
-            if sk.shape[1] != D or sk.shape[2] != Lu or Bs not in (1, B):
-                raise ValueError(f"skip {tuple(sk.shape)} does not match ({B}|1, {D}, {Lu})")
-            bc = Bs == 1 and B > 1
-            mx = f"decoder.mixers.{i}."
-            xu, pr, gx, xm = self.E(B * Lu, D), self.E(Bs * Lu, D), self.E(B * Lu, D), self.E(B * Lu, D)
-            ops.unet_up(x, m.P(f"decoder.ups.{i}.1.weight"), m.P(f"decoder.ups.{i}.1.bias"), xu, B, Li, m.stride)
-            skf = m._frames(sk, self.dt)
-            if self.own_skip[m.n_downs - 1 - i] and skf.data_ptr() == sk.data_ptr():
-                skf = skf.clone()           # a caller's tensor, not a training audio_encoder's: the backward reads it, so keep its values
-            ops.gemm_nt(skf, pk[mx + "proj.0"], m.P(mx + "proj.0.bias"), pr)
-            ops.gemm_nt(xu, pk[mx + "gate"], m.P(mx + "gate.bias"), gx)
-            ops.unet_mixer(xu, pr, bc, gx, m.P(mx + "proj.1.gamma"), xm, B, Lu)
-            y, rec = self.layer_fwd(f"decoder.layers.{i}.", xm, s, B, Lu)
-            self.ups.append((x, xu, skf, pr, gx, bc, Bs, rec, Li))
-            x, Li = y, Lu
-        self.x_out, self.Lout = x, Li
-        out = torch.empty(B, m.P("proj_out.weight").shape[0], Li, dtype=F32, device=self.dev)
-        ops.chart_head(x, m.P("proj_out.weight").view(out.shape[1], D), m.P("proj_out.bias"), out, B, Li, 0)
-        return out
 
     def decode_bwd(self, dlogits: torch.Tensor):
         """Returns (dz, ds, [dskip per skip in the caller's order])."""
@@ -347,18 +252,6 @@ class _Tape:
         ops.proj_in_bwd_input(dx, m.P("proj_emb.weight").view(D, E), dz)
         return dz, self.flush(ds), dskips
 
-    # ------------------------------------------------------------------ latent/model.py:72-76 (label_predictor)
-    def labels_fwd(self, s: torch.Tensor):
-        m = self.m
-        B = s.shape[0]
-        self.s = s
-        self.hid_pre = torch.empty(B, m.a_dim, dtype=F32, device=self.dev)
-        self.hid = torch.empty_like(self.hid_pre)
-        out = torch.empty(B, m.P("label_predictor.2.weight").shape[0], dtype=F32, device=self.dev)
-        ops.linear_small(s, m.P("label_predictor.0.weight"), m.P("label_predictor.0.bias"), self.hid, self.hid_pre, OD_ACT_SILU)
-        ops.linear_small(self.hid, m.P("label_predictor.2.weight"), m.P("label_predictor.2.bias"), out)
-        return out
-
     def labels_bwd(self, dout: torch.Tensor):
         m, g = self.m, self.g
         dout = dout.to(F32).contiguous()
@@ -379,7 +272,7 @@ class _AudioFn(torch.autograd.Function):
     def forward(ctx, tape, audio, *params):
         ctx.tape = tape
         ctx.set_materialize_grads(False)
-        skips, h = tape.audio_fwd(audio)
+        skips, h = tape.m._audio_fwd(tape, audio)
         return (*skips, h)
 
     @staticmethod
@@ -394,7 +287,7 @@ class _ChartFn(torch.autograd.Function):
     def forward(ctx, tape, chart, *params):
         ctx.tape = tape
         ctx.set_materialize_grads(False)
-        return tape.chart_fwd(chart)
+        return tape.m._chart_fwd(tape, chart)
 
     @staticmethod
     def backward(ctx, dz, ds):
@@ -409,7 +302,7 @@ class _DecodeFn(torch.autograd.Function):
     def forward(ctx, tape, n_skips, z, s, *rest):
         ctx.tape, ctx.n_skips, ctx.skip_dtypes = tape, n_skips, [t.dtype for t in rest[:n_skips]]
         ctx.set_materialize_grads(False)
-        return tape.decode_fwd(z, s, list(rest[:n_skips]))
+        return tape.m._decode_fwd(tape, z, s, rest[:n_skips], 0)
 
     @staticmethod
     def backward(ctx, dlogits):
@@ -425,7 +318,7 @@ class _LabelsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tape, s, *params):
         ctx.tape = tape
-        return tape.labels_fwd(s)
+        return tape.m._label_predictor(s, tape)
 
     @staticmethod
     def backward(ctx, dout):
@@ -458,8 +351,6 @@ def encode_chart(m, chart: torch.Tensor):
 
 def decode_logits(m, z: torch.Tensor, s: torch.Tensor, skips) -> torch.Tensor:
     skips = list(skips)
-    if len(skips) != m.n_downs:
-        raise ValueError(f"expected {m.n_downs} skips, got {len(skips)}")
     tape, params = _tape(m, "proj_emb.", "decoder.", "proj_out.")
     tape.own_skip = [not isinstance(getattr(sk.grad_fn, "tape", None), _Tape) for sk in skips]
     return _DecodeFn.apply(tape, len(skips), _f32c(z), _f32c(s), *skips, *params)

@@ -70,6 +70,11 @@ def _i32(*ts):
         assert t.dtype == torch.int32 and t.is_contiguous(), "expected contiguous int32"
 
 
+def _lens(lens, B):
+    _i32(lens)
+    assert lens.dim() == 1 and lens.shape[0] == B and lens.is_contiguous(), "lens must be a contiguous int32 [B]"
+
+
 # ---------------------------------------------------------------- GEMMs
 def gemm_nt(A, W, bias, C, epilogue=OD_EPI_NONE, accumulate=False, x3=False):
     code, W = mm_code(A.dtype, x3, W), _w(W)
@@ -411,18 +416,18 @@ def flash_attn_bwd_fused(q, k, v, o, do, lse, dq, dk, dv, B, H, L, hd, scale, ws
 
 
 # ---------------------------------------------------------------- feed-forward
-def dwconv(x, w, bias, y, B, L, ksize):
+def dwconv(x, w, bias, y, B, L, ksize, lens=None):
+    """`lens` (device int32 [B]): per sequence of valid length lens[b]; frames >= lens[b] of y come back as 0."""
     C = x.shape[1]
     _f32(w, bias)
-    _lib.lib().od_dwconv(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, L, C, ksize, _stream(x))
+    if lens is None:
+        return _lib.lib().od_dwconv(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, L, C, ksize, _stream(x))
+    _i32(lens)
+    _lib.lib().od_dwconv_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, L, C, ksize, _stream(x))
 
 
 def dwconv_varlen(x, w, bias, y, lens, B, L, ksize):
-    """dwconv per sequence of valid length lens[b] (device int32 [B]); frames >= lens[b] of y come back as 0."""
-    C = x.shape[1]
-    _f32(w, bias)
-    _i32(lens)
-    _lib.lib().od_dwconv_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, L, C, ksize, _stream(x))
+    dwconv(x, w, bias, y, B, L, ksize, lens)
 
 
 def dwconv_bwd(x, w, dy, dx, dw, db, B, L, ksize):
@@ -653,18 +658,27 @@ def cast_rows(src, dst):
     _lib.lib().od_cast_rows(dt_code(src.dtype), _p(src), dt_code(dst.dtype), _p(dst), src.numel(), _stream(src))
 
 
-# ---------------------------------------------------------------- latent model, inference path
-def spec_features_conv(audio, w1, b1, g1, w2, b2, g2, out, eps=1e-6):
+# ---------------------------------------------------------------- latent model, forward.  `lens` (device int32 [B], the valid frames
+# of each sequence at the level the call reads) selects the varlen entry point: frames past them come back as exact zeros
+def spec_features_conv(audio, w1, b1, g1, w2, b2, g2, out, eps=1e-6, lens=None):
     B, F, L = audio.shape
     _f32(audio, w1, b1, g1, w2, b2, g2)
-    _lib.lib().od_spec_features_conv(dt_code(out.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2),
-                                     _p(out), _ld(out), B, F, L, eps, _stream(audio))
+    if lens is None:
+        return _lib.lib().od_spec_features_conv(dt_code(out.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2),
+                                                _p(out), _ld(out), B, F, L, eps, _stream(audio))
+    _lens(lens, B)
+    _lib.lib().od_spec_features_conv_varlen(dt_code(out.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2),
+                                            _p(out), _ld(out), _p(lens), B, F, L, eps, _stream(audio))
 
 
-def rmsnorm_affine_film(x, gamma, ssg, y, B, L, act=OD_ACT_NONE, eps=1e-6):
+def rmsnorm_affine_film(x, gamma, ssg, y, B, L, act=OD_ACT_NONE, eps=1e-6, lens=None):
     _f32(gamma, ssg)
-    _lib.lib().od_rmsnorm_affine_film(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(y), _ld(y), B, L, x.shape[1],
-                                      eps, act, _stream(x))
+    if lens is None:
+        return _lib.lib().od_rmsnorm_affine_film(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(y), _ld(y), B, L, x.shape[1],
+                                                 eps, act, _stream(x))
+    _lens(lens, B)
+    _lib.lib().od_rmsnorm_affine_film_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(y), _ld(y), _p(lens), B, L,
+                                             x.shape[1], eps, act, _stream(x))
 
 
 def rmsnorm_affine_gate_residual(x, h, gamma, ssg, xo, B, L, eps=1e-6):
@@ -673,35 +687,58 @@ def rmsnorm_affine_gate_residual(x, h, gamma, ssg, xo, B, L, eps=1e-6):
                                                _ld(xo), B, L, x.shape[1], eps, _stream(x))
 
 
-def unet_mixer(x, p, p_bcast, gx, gamma, xo, B, L, eps=1e-6):
+def unet_mixer(x, p, p_bcast, gx, gamma, xo, B, L, eps=1e-6, prow=None):
+    """`prow` (device int32 [B]): decoder row b reads frame l of skip row prow[b], and p_bcast is not looked at."""
     _f32(gamma)
-    _lib.lib().od_unet_mixer(dt_code(x.dtype), _p(x), _ld(x), _p(p), _ld(p), int(p_bcast), _p(gx), _ld(gx), _p(gamma),
-                             _p(xo), _ld(xo), B, L, x.shape[1], eps, _stream(x))
+    if prow is None:
+        return _lib.lib().od_unet_mixer(dt_code(x.dtype), _p(x), _ld(x), _p(p), _ld(p), int(p_bcast), _p(gx), _ld(gx), _p(gamma),
+                                        _p(xo), _ld(xo), B, L, x.shape[1], eps, _stream(x))
+    _lens(prow, B)
+    _lib.lib().od_unet_mixer_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(p), _ld(p), _p(prow), _p(gx), _ld(gx), _p(gamma),
+                                    _p(xo), _ld(xo), B, L, x.shape[1], eps, _stream(x))
 
 
-def unet_down(x, w, bias, y, B, Lo, stride):
+def unet_down(x, w, bias, y, B, Lo, stride, lens=None):
+    """lens: valid frames at the INPUT level (Lo * stride)."""
     _f32(w, bias)
-    _lib.lib().od_unet_down(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, Lo, x.shape[1], stride,
-                            _stream(x))
+    if lens is None:
+        return _lib.lib().od_unet_down(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, Lo, x.shape[1], stride,
+                                       _stream(x))
+    _lens(lens, B)
+    _lib.lib().od_unet_down_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Lo, x.shape[1],
+                                   stride, _stream(x))
 
 
-def unet_up(x, w, bias, y, B, Li, stride):
+def unet_up(x, w, bias, y, B, Li, stride, lens=None):
+    """lens: valid frames at the INPUT level (Li)."""
     _f32(w, bias)
-    _lib.lib().od_unet_up(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, Li, x.shape[1], stride,
-                          _stream(x))
+    if lens is None:
+        return _lib.lib().od_unet_up(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), B, Li, x.shape[1], stride,
+                                     _stream(x))
+    _lens(lens, B)
+    _lib.lib().od_unet_up_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Li, x.shape[1],
+                                 stride, _stream(x))
 
 
-def chart_head(x, W, bias, out, B, L, n_sigmoid, rms=False, eps=1e-6):
+def chart_head(x, W, bias, out, B, L, n_sigmoid, rms=False, eps=1e-6, lens=None):
     _f32(W, bias, out)
     N = W.shape[0]
-    _lib.lib().od_chart_head(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(out), B, L, x.shape[1], N, n_sigmoid,
-                             int(rms), eps, _stream(x))
+    if lens is None:
+        return _lib.lib().od_chart_head(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(out), B, L, x.shape[1], N, n_sigmoid,
+                                        int(rms), eps, _stream(x))
+    _lens(lens, B)
+    _lib.lib().od_chart_head_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(out), _p(lens), B, L, x.shape[1], N,
+                                    n_sigmoid, int(rms), eps, _stream(x))
 
 
-def attn_pool(scores, values, out, B, L, heads, hd):
+def attn_pool(scores, values, out, B, L, heads, hd, lens=None):
     _f32(out)
-    _lib.lib().od_attn_pool(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), B, L, heads, hd,
-                            _stream(scores))
+    if lens is None:
+        return _lib.lib().od_attn_pool(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), B, L, heads,
+                                       hd, _stream(scores))
+    _lens(lens, B)
+    _lib.lib().od_attn_pool_varlen(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), _p(lens), B, L,
+                                   heads, hd, _stream(scores))
 
 
 # ---------------------------------------------------------------- latent model, backward kernels.  Sums over frames (dgamma, dssg, dw,
@@ -805,64 +842,33 @@ def proj_in_bwd_input(dx, W, dxt):
     _lib.lib().od_proj_in_bwd_input(dt_code(dx.dtype), _p(dx), _ld(dx), _p(W), _p(dxt), B, E, L, dx.shape[1], _stream(dx))
 
 
-# ---------------------------------------------------------------- latent model, varlen forms (lens: device int32 [B], the valid
-# frames of each sequence at the level the call reads; frames past them come back as exact zeros)
-def _lens(lens, B):
-    _i32(lens)
-    assert lens.dim() == 1 and lens.shape[0] == B and lens.is_contiguous(), "lens must be a contiguous int32 [B]"
-
-
+# ---------------------------------------------------------------- latent model, varlen names: the forward wrappers above with `lens`
 def spec_features_conv_varlen(audio, w1, b1, g1, w2, b2, g2, out, lens, eps=1e-6):
-    B, F, L = audio.shape
-    _f32(audio, w1, b1, g1, w2, b2, g2)
-    _lens(lens, B)
-    _lib.lib().od_spec_features_conv_varlen(dt_code(out.dtype), _p(audio), _p(w1), _p(b1), _p(g1), _p(w2), _p(b2), _p(g2),
-                                            _p(out), _ld(out), _p(lens), B, F, L, eps, _stream(audio))
+    spec_features_conv(audio, w1, b1, g1, w2, b2, g2, out, eps, lens)
 
 
 def rmsnorm_affine_film_varlen(x, gamma, ssg, y, lens, B, L, act=OD_ACT_NONE, eps=1e-6):
-    _f32(gamma, ssg)
-    _lens(lens, B)
-    _lib.lib().od_rmsnorm_affine_film_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(gamma), _p(ssg), _p(y), _ld(y), _p(lens), B, L,
-                                             x.shape[1], eps, act, _stream(x))
+    rmsnorm_affine_film(x, gamma, ssg, y, B, L, act, eps, lens)
 
 
 def unet_mixer_varlen(x, p, prow, gx, gamma, xo, B, L, eps=1e-6):
-    """unet_mixer where decoder row b reads frame l of skip row prow[b] (device int32 [B])."""
-    _f32(gamma)
-    _lens(prow, B)
-    _lib.lib().od_unet_mixer_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(p), _ld(p), _p(prow), _p(gx), _ld(gx), _p(gamma),
-                                    _p(xo), _ld(xo), B, L, x.shape[1], eps, _stream(x))
+    unet_mixer(x, p, False, gx, gamma, xo, B, L, eps, prow)
 
 
 def unet_down_varlen(x, w, bias, y, lens, B, Lo, stride):
-    """lens: valid frames at the INPUT level (Lo * stride)."""
-    _f32(w, bias)
-    _lens(lens, B)
-    _lib.lib().od_unet_down_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Lo, x.shape[1],
-                                   stride, _stream(x))
+    unet_down(x, w, bias, y, B, Lo, stride, lens)
 
 
 def unet_up_varlen(x, w, bias, y, lens, B, Li, stride):
-    """lens: valid frames at the INPUT level (Li)."""
-    _f32(w, bias)
-    _lens(lens, B)
-    _lib.lib().od_unet_up_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(w), _p(bias), _p(y), _ld(y), _p(lens), B, Li, x.shape[1],
-                                 stride, _stream(x))
+    unet_up(x, w, bias, y, B, Li, stride, lens)
 
 
 def chart_head_varlen(x, W, bias, out, lens, B, L, n_sigmoid, rms=False, eps=1e-6):
-    _f32(W, bias, out)
-    _lens(lens, B)
-    _lib.lib().od_chart_head_varlen(dt_code(x.dtype), _p(x), _ld(x), _p(W), _p(bias), _p(out), _p(lens), B, L, x.shape[1],
-                                    W.shape[0], n_sigmoid, int(rms), eps, _stream(x))
+    chart_head(x, W, bias, out, B, L, n_sigmoid, rms, eps, lens)
 
 
 def attn_pool_varlen(scores, values, out, lens, B, L, heads, hd):
-    _f32(out)
-    _lens(lens, B)
-    _lib.lib().od_attn_pool_varlen(dt_code(scores.dtype), _p(scores), _ld(scores), _p(values), _ld(values), _p(out), _p(lens), B, L,
-                                   heads, hd, _stream(scores))
+    attn_pool(scores, values, out, B, L, heads, hd, lens)
 
 
 # ---------------------------------------------------------------- latent model, training-step kernels (fp32; deterministic sums)
