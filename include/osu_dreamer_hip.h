@@ -330,6 +330,14 @@ int od_loss_grad_varlen(const float* xt, const float* x1, const float* u, const 
 /* out[0..3] = loss, osl, del, u_mape; du[b] = dLoss/du_pred. */
 int od_loss_finalize(const float* sums, const float* dsq, const float* u, float* out, float* du, int B, float c0,
                      float osl_w, float del_w, void* stream);
+/* per map g of a validation group of G (rows [offs[g], offs[g+1]) of sums / dsq / u): out[g][0..3] = loss, osl, del, u_mape as
+ * od_loss_finalize returns them on those rows alone, bit for bit (same summation order); out is (G, 4).  No du: validation has no
+ * backward.  offs is G + 1 HOST int32 (the caller cut the rows itself): the launcher checks them and hands them to the kernel in its
+ * arguments, so nothing is copied or waited for.  OD_ERR_ARG: a null offs, G < 1, offs[0] < 0 or an empty map (offs[g+1] <= offs[g]).
+ * replaces: models/diffusion/train.py:128-139 (validation_step on one map's val_batches segments) with the means of :87-101, once per
+ * map of a batch of maps. */
+int od_loss_finalize_groups(const float* sums, const float* dsq, const float* u, const int* offs, float* out, int G, float c0,
+                            float osl_w, float del_w, void* stream);
 /* x -= eta[0] * u[b] * v  (eta is a device scalar so the step is graph-capturable).  replaces: model.py:136. */
 int od_sampler_step(float* x, const float* u, const float* v, const float* eta, int B, int E, int L, void* stream);
 /* eta[0] = 1 - (sqrt(c0)/max(mean(u), sqrt(c0)+1e-6))^(1/num_steps); also eta[1] = mean(u).  replaces: model.py:131-132. */

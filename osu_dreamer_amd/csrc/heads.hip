@@ -396,6 +396,30 @@ __global__ void loss_finalize_kernel(const float* __restrict__ sums, const float
     if (lane == 0) { out[0] = osl_w * osl + del_w * del; out[1] = osl; out[2] = del; out[3] = mape; }
 }
 
+// loss_finalize_kernel per map of a validation group, one wave per map g of a launch: rows [offs.v[g], offs.v[g + 1]) in exactly that
+// kernel's order (lane j takes rows r0 + j, r0 + j + 64, ..., then od_wave_sum, then the division by the map's row count), so out[g][0..3]
+// is bit for bit what od_loss_finalize returns on the map's rows alone.  No du: validation has no backward.  The row offsets are host
+// integers and travel in the kernel's arguments, OD_LOSS_GROUPS_PER_LAUNCH maps a launch; the launcher refuses an empty map, and a wave
+// that met one all the same writes nothing rather than divide by zero.
+#define OD_LOSS_GROUPS_PER_LAUNCH 255
+struct LossGroupOffs { int v[OD_LOSS_GROUPS_PER_LAUNCH + 1]; };
+
+__global__ void loss_finalize_groups_kernel(const float* __restrict__ sums, const float* __restrict__ dsq, const float* __restrict__ u,
+                                            LossGroupOffs offs, float* __restrict__ out, float c0, float osl_w, float del_w) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int r0 = offs.v[g], n = offs.v[g + 1] - r0;
+    if (n < 1) return;
+    float osl = 0.f, del = 0.f, mape = 0.f;
+    for (int b = lane; b < n; b += 64) {
+        const float den = dsq[r0 + b] + c0, ut = sqrtf(den);
+        osl += sums[(r0 + b) * 3 + 0] / den;
+        del += sums[(r0 + b) * 3 + 1];
+        mape += fabsf((u[r0 + b] - ut) / ut);
+    }
+    osl = od_wave_sum(osl) / (float)n; del = od_wave_sum(del) / (float)n; mape = od_wave_sum(mape) / (float)n;
+    if (lane == 0) { out[4 * g + 0] = osl_w * osl + del_w * del; out[4 * g + 1] = osl; out[4 * g + 2] = del; out[4 * g + 3] = mape; }
+}
+
 __global__ __launch_bounds__(256) void sampler_step_kernel(float* __restrict__ x, const float* __restrict__ u,
                                                            const float* __restrict__ v, const float* __restrict__ eta, int EL) {
     const int b = blockIdx.y;
@@ -587,6 +611,21 @@ extern "C" int od_loss_finalize(const float* sums, const float* dsq, const float
                                 float osl_w, float del_w, void* stream) {
     OD_LAUNCH(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, dsq, u, out, du, B, c0, osl_w, del_w);
     OD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int od_loss_finalize_groups(const float* sums, const float* dsq, const float* u, const int* offs, float* out, int G, float c0,
+                                       float osl_w, float del_w, void* stream) {
+    if (!offs || G < 1 || offs[0] < 0) return OD_ERR_ARG;
+    for (int g = 0; g < G; g++)
+        if (offs[g + 1] <= offs[g]) return OD_ERR_ARG;            // an empty map has no mean
+    for (int g0 = 0; g0 < G; g0 += OD_LOSS_GROUPS_PER_LAUNCH) {
+        const int n = G - g0 < OD_LOSS_GROUPS_PER_LAUNCH ? G - g0 : OD_LOSS_GROUPS_PER_LAUNCH;
+        LossGroupOffs a;
+        for (int i = 0; i <= OD_LOSS_GROUPS_PER_LAUNCH; i++) a.v[i] = offs[g0 + (i < n ? i : n)];
+        OD_LAUNCH(loss_finalize_groups_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, sums, dsq, u, a, out + 4 * (size_t)g0, c0, osl_w, del_w);
+        OD_CHECK_LAUNCH();
+    }
     return 0;
 }
 

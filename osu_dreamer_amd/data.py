@@ -71,6 +71,19 @@ class RaggedLatentBatch(NamedTuple):
     lengths: torch.Tensor  # (N,) int64, on the host
 
 
+class RaggedLatentValBatch(NamedTuple):
+    """G whole held-out maps for the denoiser's validation (resident.ResidentLatentValFeed), each already cut into the val_batches
+    segments `DiffusionTrainer.validation_step` cuts a map into: with seg_g = L_g // val_batches, row offs[g] + j is frames
+    [j * seg_g, (j + 1) * seg_g) of map g's z and of its mapset's h, zeros behind seg_g up to Lpad; every row of map g has length seg_g
+    (>= 1).  R = G * val_batches rows.  What `DiffusionTrainer.validation_step` accepts beside the batch-1 tuple."""
+    h: torch.Tensor        # (R, A, Lpad)
+    z: torch.Tensor        # (R, E, Lpad)
+    s: torch.Tensor        # (G, S)
+    labels: torch.Tensor   # (G, NUM_LABELS)
+    lengths: torch.Tensor  # (R,) int64, on the host
+    offs: torch.Tensor     # (G + 1,) int64, on the host: map g's rows are [offs[g], offs[g + 1])
+
+
 class RaggedBeatmapBatch(NamedTuple):
     """G whole held-out maps of different lengths for the latent model's validation (resident.ResidentBeatmapValFeed), padded as
     `LatentTrainer.pad_batch` pads each of them alone: map g has lengths[g] frames, then its last frame repeated up to

@@ -121,8 +121,9 @@ class Trainer:
         return torch.autocast(device.type, enabled=False)
 
     def _to(self, batch, device):
-        if hasattr(batch, "lengths"):      # a ragged batch: the lengths stay on the host, the engine plans its varlen calls with them
-            return type(batch)(*(t if k == "lengths" else t.to(device, non_blocking=True) for k, t in zip(batch._fields, batch)))
+        if hasattr(batch, "lengths"):      # a ragged batch: the lengths (and a group's row offsets) stay on the host, the engine plans its
+            host = ("lengths", "offs")     # varlen calls with them
+            return type(batch)(*(t if k in host else t.to(device, non_blocking=True) for k, t in zip(batch._fields, batch)))
         return tuple(t.to(device, non_blocking=True) for t in batch)
 
     def save_checkpoint(self, path, module, opt, sched):
@@ -148,12 +149,27 @@ class Trainer:
         by_epoch = getattr(module, "validates_by_epoch", False)
         if by_epoch:
             module.on_validation_epoch_start()
-        for i, batch in enumerate(datamodule.val_dataloader()):
-            if self.limit_val_batches is not None and i >= self.limit_val_batches:
+        loader = datamodule.val_dataloader()
+        # a feed that groups maps (resident.ResidentLatentValFeed) plans over the first limit_val_batches MAPS itself: the limit keeps
+        # meaning maps, as with the batch-1 loaders, where it counts batches
+        by_maps = hasattr(loader, "limit")
+        if by_maps:
+            loader.limit(self.limit_val_batches)
+        for i, batch in enumerate(loader):
+            if not by_maps and self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
             with contextlib.nullcontext() if by_epoch else self._autocast(device):
                 logs = module.validation_step(self._to(batch, device), i)
-            if not by_epoch:
+            if by_epoch:
+                continue
+            vals = list(logs.values())
+            if vals and vals[0].dim() == 1:           # a group's per-map values, name -> (G,): ONE read, then the maps in their order
+                table = torch.stack(vals).cpu().tolist()
+                for j in range(len(table[0])):
+                    for k, row in zip(logs, table):
+                        sums[k] = sums.get(k, 0.0) + row[j]
+                n += len(table[0])
+            else:
                 for k, v in logs.items():
                     sums[k] = sums.get(k, 0.0) + float(v)
                 n += 1
@@ -391,14 +407,33 @@ def pop_resident(data: Dict[str, Any], trainer: "Trainer") -> Optional[Dict[str,
     return dict(device=_lib.training_device(trainer.local_rank, "data.resident"), resident_max_gb=max_gb)
 
 
-def build_latent_data(data: Dict[str, Any], trainer: "Trainer", style_only: bool = False, **shard):
+def pop_resident_val(data: Dict[str, Any], resident: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """Takes `resident_val` and `val_frame_budget` out of the `data:` block, as the resident data modules' keywords.  Both validate from a
+    second resident store: without `resident` (pop_resident's answer None) either key is refused, and so is a budget without `resident_val`."""
+    resident_val, val_budget = data.pop("resident_val", False), data.pop("val_frame_budget", None)
+    if resident is None:
+        if resident_val or val_budget is not None:
+            raise ValueError("data.resident_val / data.val_frame_budget validate from the resident store: set data.resident: true, or drop "
+                             "the keys")
+        return {}
+    if val_budget is not None and not resident_val:
+        raise ValueError("data.val_frame_budget sizes the groups of the resident validation: set data.resident_val: true, or drop the key")
+    return dict(resident_val=bool(resident_val), val_frame_budget=val_budget)
+
+
+def build_latent_data(data: Dict[str, Any], trainer: "Trainer", style_only: bool = False, val_batches: Optional[int] = None, **shard):
     """The `data:` block -> its data module.  `data.resident: true` keeps the training set on the device (resident.py: every file read once,
-    batches gathered by od_feed_gather), within `data.resident_max_gb` when that is set; fit-style's store holds the style fields only."""
+    batches gathered by od_feed_gather), within `data.resident_max_gb` when that is set; fit-style's store holds the style fields only.
+    `data.resident_val: true` (with data.resident, fit-denoiser) keeps the held-out maps there too and validates them in groups of at most
+    `data.val_frame_budget` padded frames (default 131 072), each map cut into the model's `val_batches` segments and padded to
+    `data.pad_multiple`."""
     resident = pop_resident(data, trainer)
+    val = pop_resident_val(data, resident)
     if resident is None:
         return LatentDataModule(**data, **shard)
     from .resident import STYLE_FIELDS, ALL_FIELDS, ResidentLatentDataModule
-    return ResidentLatentDataModule(**data, **shard, **resident, fields=STYLE_FIELDS if style_only else ALL_FIELDS)
+    return ResidentLatentDataModule(**data, **shard, **resident, **val, val_batches=val_batches,
+                                    fields=STYLE_FIELDS if style_only else ALL_FIELDS)
 
 
 def load_config(config: str, overrides: Dict[str, Any]) -> Dict[str, Any]:
@@ -424,7 +459,7 @@ def fit_denoiser(config: str = DEFAULT_CONFIG, ckpt_path: Optional[str] = None, 
         raise RuntimeError(f"fit_denoiser() with trainer.devices={devices} must run inside a rank: use `python -m osu_dreamer_amd "
                            f"fit-denoiser` (it starts the {devices} ranks) or `torchrun --nproc-per-node {devices}`")
     module, trainer = build_from_config(cfg)
-    data = build_latent_data(dict(cfg["data"]), trainer, rank=trainer.rank, world_size=trainer.world)
+    data = build_latent_data(dict(cfg["data"]), trainer, val_batches=module.val_batches, rank=trainer.rank, world_size=trainer.world)
     trainer.fit(module, data, ckpt_path=ckpt_path)
     return module, trainer
 
@@ -463,18 +498,12 @@ def build_beatmap_data(data: Dict[str, Any], trainer: "Trainer", val_pad_multipl
     validates them in ragged groups of at most `data.val_frame_budget` padded frames, each map padded to `val_pad_multiple` (the
     trainer's 2 x chunk_size)."""
     from .data import BeatmapDataModule
-    resident_val, val_budget = data.pop("resident_val", False), data.pop("val_frame_budget", None)
     resident = pop_resident(data, trainer)
+    val = pop_resident_val(data, resident)
     if resident is None:
-        if resident_val or val_budget is not None:
-            raise ValueError("data.resident_val / data.val_frame_budget validate from the resident store: set data.resident: true, or drop "
-                             "the keys")
         return BeatmapDataModule(**data)
-    if val_budget is not None and not resident_val:
-        raise ValueError("data.val_frame_budget sizes the groups of the resident validation: set data.resident_val: true, or drop the key")
     from .resident import ResidentBeatmapDataModule
-    return ResidentBeatmapDataModule(**data, **resident, resident_val=bool(resident_val), val_frame_budget=val_budget,
-                                     val_pad_multiple=val_pad_multiple)
+    return ResidentBeatmapDataModule(**data, **resident, **val, val_pad_multiple=val_pad_multiple)
 
 
 def fit_latent(config: str = DEFAULT_LATENT_CONFIG, ckpt_path: Optional[str] = None, **overrides):

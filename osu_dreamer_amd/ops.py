@@ -573,6 +573,17 @@ def loss_finalize(sums, dsq, u, out, du, c0, osl_w, del_w):
     _lib.lib().od_loss_finalize(_p(sums), _p(dsq), _p(u), _p(out), _p(du), B, c0, osl_w, del_w, _stream(u))
 
 
+def loss_finalize_groups(sums, dsq, u, offs, out, c0, osl_w, del_w):
+    """out (G, 4): per map g, loss_finalize's (loss, osl, del, u_mape) over rows [offs[g], offs[g+1]) of sums / dsq / u alone, bit for bit.
+    offs: G + 1 host ints (a sequence, or an int32 tensor on the host) that cover rows of u only; an empty map is refused."""
+    _f32(sums, dsq, u, out)
+    offs = torch.as_tensor(offs, dtype=torch.int32).contiguous()
+    assert offs.device.type == "cpu" and offs.dim() == 1 and offs.numel() >= 1, "offs: G + 1 ints on the host"
+    G = offs.numel() - 1
+    assert out.numel() >= 4 * G and int(offs[-1]) <= u.shape[0] and sums.numel() >= 3 * u.shape[0] and dsq.numel() >= u.shape[0]
+    _lib.lib().od_loss_finalize_groups(_p(sums), _p(dsq), _p(u), _p(offs), _p(out), G, c0, osl_w, del_w, _stream(u))
+
+
 def sampler_step(x, u, v, eta):
     B, E, L = x.shape
     _f32(x, u, v, eta)

@@ -13,6 +13,9 @@ that would not, before anything is allocated.
 The feed follows the host loader's rules in its three modes (an integer seq_len: fixed windows; seq_len None with batch_size N: N whole
 maps per batch; batch_frames: frame-budget batches cut by data.cut_batches), with one difference that comes with planning a whole epoch at
 once: the order is a full permutation of the epoch's samples instead of a shuffle buffer's, so `shuffle_buffer_size` has no meaning here.
+With `data.resident_val` the denoiser's held-out maps live in a second store too and are validated in groups of whole maps
+(`ResidentLatentValFeed`): every map cut into the trainer's val_batches segments by the same gather, one ragged no-grad forward per group,
+and od_loss_finalize_groups for each map's own means.
 
 The latent model's trainer has the same feed over the pre-processed beatmaps (the second half of this file): `BeatmapDataModule` opens the
 mapset's whole `spec.npy` and the map's npz for every sample of every epoch, widens both to float64 and keeps one window.  Here
@@ -32,7 +35,7 @@ import torch
 
 from . import _lib, ops
 from .data import (A_DIM, NUM_LABELS, X_DIM, Batch, BeatmapDataModule, BeatmapDataset, LatentBatch, LatentDataModule, LatentDataset,
-                   RaggedBeatmapBatch, RaggedLatentBatch, _roundup, cut_batches)
+                   RaggedBeatmapBatch, RaggedLatentBatch, RaggedLatentValBatch, _roundup, cut_batches)
 
 ALL_FIELDS = ("h", "z", "s", "labels")
 STYLE_FIELDS = ("s", "labels")
@@ -196,10 +199,11 @@ class ResidentLatentStore:
 
     `fields` without "h" / "z" (the style model's feed) reads the `s` and `labels` members only and never opens h.npy; the lengths then
     come from the header of the `z` member (its array is not read).  The upload goes through two pinned staging buffers of `staging_bytes`
-    each, not through a host copy of the dataset.  `max_bytes`: refuse — before anything is allocated — a store that needs more."""
+    each, not through a host copy of the dataset.  `max_bytes`: refuse — before anything is allocated — a store that needs more, counting
+    `reserved_bytes` that another store under the same limit already holds."""
 
     def __init__(self, mapsets: Sequence[Path], device, fields: Sequence[str] = ALL_FIELDS, rank: int = 0, world_size: int = 1,
-                 max_bytes: Optional[int] = None, staging_bytes: int = 32 << 20):
+                 max_bytes: Optional[int] = None, staging_bytes: int = 32 << 20, reserved_bytes: int = 0):
         self.device = torch.device(device)
         self.fields = tuple(fields)
         if not set(self.fields) <= set(ALL_FIELDS) or not {"s", "labels"} <= set(self.fields) or ("h" in self.fields) != ("z" in self.fields):
@@ -238,7 +242,7 @@ class ResidentLatentStore:
                 self.z_base[i] = elems
                 elems += self.emb_dim * int(self.lengths[i])
         self.nbytes = 4 * (elems + n * (self.style_dim + NUM_LABELS))
-        _refuse_over_limit(self.nbytes, n, max_bytes)
+        _refuse_over_limit(self.nbytes, n, max_bytes, reserved_bytes)
         # ---- allocate and fill
         self.data = torch.empty(max(elems, 1), dtype=torch.float32, device=self.device)
         s_host, labels_host = np.empty((n, self.style_dim), dtype=np.float32), np.empty((n, NUM_LABELS), dtype=np.float32)
@@ -387,16 +391,117 @@ class ResidentFeed(_EpochFeed):
         return LatentBatch(h, z, s, labels)
 
 
+DEFAULT_VAL_FRAME_BUDGET = 1 << 17     # padded frames of a validation group: half of a training step of 32 windows x 8192 frames
+
+
+class ResidentLatentValFeed:
+    """Re-iterable over one validation epoch of the held-out maps in `store`, whole maps in groups (`data.RaggedLatentValBatch`).
+
+    `DiffusionTrainer.validation_step` cuts a map of L frames into `val_batches` segments of seg = L // val_batches frames and evaluates
+    them as one batch.  The plan here is made once, from the store's lengths: the maps with seg >= 1 are packed longest first
+    (encode_latents.pack) into groups whose padded size, val_batches x G x (the longest seg rounded up to `pad_multiple`), stays within
+    `frame_budget`; a map over the budget goes alone.  A group is built by two od_feed_gather launches behind one descriptor copy: row
+    val_batches * g + j takes seg_g frames from frame j * seg_g of map g's z and of its mapset's h — bit for bit the slices
+    validation_step cuts from the host loader's tensors — and zeros behind them; s and labels come from index_select.
+
+    A map of fewer than `val_batches` frames has seg = 0, no frame to evaluate: such maps are not grouped and follow the groups one by
+    one as the host loader's batch-1 tuple (h, z, s, labels), which validation_step treats as it always has (it refuses a map without a
+    frame per segment, from either loader).
+
+    `limit(n)`: plan over the first n held-out maps of the host loader's order (the store's), which is what `limit_val_batches` means."""
+
+    def __init__(self, store: ResidentLatentStore, val_batches: int, pad_multiple: int = 64, frame_budget: Optional[int] = None):
+        if not store.has_frames:
+            raise ValueError("the resident validation of the denoiser gathers h and z: the store must hold them (fields = ALL_FIELDS)")
+        if val_batches < 1 or pad_multiple < 1:
+            raise ValueError(f"invalid {val_batches=} / {pad_multiple=}")
+        self.store, self.val_batches, self.pad_multiple = store, int(val_batches), int(pad_multiple)
+        self.frame_budget = int(DEFAULT_VAL_FRAME_BUDGET if frame_budget is None else frame_budget)
+        if self.frame_budget < 1:
+            raise ValueError(f"data.val_frame_budget must be at least 1 frame, got {frame_budget}")
+        self.segs = store.lengths // self.val_batches
+        self.pin = store.device.type == "cuda"
+        self.limit(None)
+
+    def limit(self, n: Optional[int]) -> "ResidentLatentValFeed":
+        """Plan over the first `n` maps of the store (None: all of them)."""
+        from .encode_latents import pack
+        self.count = len(self.store) if n is None else max(0, min(int(n), len(self.store)))
+        first = np.arange(self.count)
+        whole = first[self.segs[:self.count] >= 1]
+        padded = self.val_batches * _roundup_all(self.segs[whole], self.pad_multiple)
+        self.groups: List[np.ndarray] = [whole[g] for g in pack(padded.tolist(), self.frame_budget)]
+        self.short: np.ndarray = first[self.segs[:self.count] < 1]
+        return self
+
+    def __len__(self):
+        return len(self.groups) + len(self.short)
+
+    def padded_share(self) -> List[float]:
+        """Per group, the share of its R x Lpad frames that belong to no segment (zeros)."""
+        vb = self.val_batches
+        return [1.0 - float(vb * self.segs[g].sum()) / (vb * len(g) * _roundup(int(self.segs[g].max()), self.pad_multiple)) for g in self.groups]
+
+    def gather(self, maps: np.ndarray) -> RaggedLatentValBatch:
+        """The device batch of one group.  The descriptors (h base, h channel stride, z base, z channel stride per row, the map indices, the
+        rows' lengths as int32) travel as one copy (pack_descriptors)."""
+        st, vb = self.store, self.val_batches
+        seg = self.segs[maps]
+        Lpad = _roundup(int(seg.max()), self.pad_multiple)
+        rows = np.repeat(maps, vb)
+        lens = np.repeat(seg, vb)
+        starts = np.tile(np.arange(vb, dtype=np.int64), len(maps)) * lens
+        map_lens = st.lengths[rows]                             # z's channel stride
+        _assert_inside_maps(map_lens, starts, lens, Lpad)
+        h_base, h_stride, z_base, z_stride, idx, lens32 = pack_descriptors(
+            st.device, self.pin, i64=(st.h_base[rows] + starts, st.h_stride[rows], st.z_base[rows] + starts, map_lens, maps), i32=(lens,))
+        R = len(rows)
+        h = torch.empty(R, st.a_dim, Lpad, dtype=torch.float32, device=st.device)
+        z = torch.empty(R, st.emb_dim, Lpad, dtype=torch.float32, device=st.device)
+        ops.feed_gather(st.data, h_base, h_stride, lens32, h)
+        ops.feed_gather(st.data, z_base, z_stride, lens32, z)
+        return RaggedLatentValBatch(h, z, st.s.index_select(0, idx), st.labels.index_select(0, idx), torch.from_numpy(lens.astype(np.int64)),
+                                    torch.arange(0, R + 1, vb, dtype=torch.int64))
+
+    def gather_one(self, m: int):
+        """Map m whole, as the host loader's batch-1 tuple: (h (1, A, Lh) — the mapset's whole h — z (1, E, L), s (1, S), labels (1, 5))."""
+        st = self.store
+        Lh, L = int(st.h_stride[m]), int(st.lengths[m])
+        h = st.data[int(st.h_base[m]):int(st.h_base[m]) + st.a_dim * Lh].view(1, st.a_dim, Lh)
+        z = st.data[int(st.z_base[m]):int(st.z_base[m]) + st.emb_dim * L].view(1, st.emb_dim, L)
+        return h, z, st.s[m:m + 1], st.labels[m:m + 1]
+
+    def __iter__(self) -> Iterator:
+        for g in self.groups:
+            yield self.gather(g)
+        for m in self.short.tolist():
+            yield self.gather_one(m)
+
+
+def _roundup_all(n: np.ndarray, m: int) -> np.ndarray:
+    return (n + m - 1) // m * m
+
+
 class ResidentLatentDataModule:
     """`LatentDataModule` with the training set resident on `device`: the same constructor keys (the YAML `data:` block) and the same three
-    feed modes, plus `device`, `fields` (STYLE_FIELDS for fit-style: s and labels only) and `resident_max_gb`.  `num_workers` serves the
-    denoiser's validation loader only (that one stays the host loader: validation reads whole maps once per check) and
-    `shuffle_buffer_size` nothing: an epoch is a full permutation."""
+    feed modes, plus `device`, `fields` (STYLE_FIELDS for fit-style: s and labels only), `resident_max_gb`, and `resident_val` with
+    `val_frame_budget` and `val_batches`.  Unless `resident_val`, the denoiser's validation stays the host loader (whole maps read once
+    per check), which is all `num_workers` still serves; `shuffle_buffer_size` serves nothing: an epoch is a full permutation.  With
+    `resident_val` the held-out maps — all of them on every rank, as the host loader hands them out — go, on first use, into a second
+    store under the same `resident_max_gb`, and validation reads groups of whole maps from it (ResidentLatentValFeed), each map cut into
+    the trainer's `val_batches` segments (fit-denoiser passes the model's)."""
 
     def __init__(self, batch_size: int, seq_len: Optional[int], num_workers: int = 0, max_val_count: int = 512, max_val_frac: float = .3,
                  data_path: str = "./data", shuffle_buffer_size: int = 1, max_per_map: int = -1, rank: int = 0, world_size: int = 1,
                  max_len: Optional[int] = None, pad_multiple: int = 64, batch_frames: Optional[int] = None, bucket_pool: Optional[int] = None,
-                 device=None, fields: Sequence[str] = ALL_FIELDS, resident_max_gb: Optional[float] = None):
+                 device=None, fields: Sequence[str] = ALL_FIELDS, resident_max_gb: Optional[float] = None, resident_val: bool = False,
+                 val_frame_budget: Optional[int] = None, val_batches: Optional[int] = None):
+        if resident_val and tuple(fields) != ALL_FIELDS:
+            raise ValueError("data.resident_val validates the denoiser from h and z: a style-only store validates from its own table already")
+        if resident_val and val_batches is None:
+            raise ValueError("data.resident_val cuts every held-out map as the trainer does: val_batches (the model's) is needed")
+        if val_frame_budget is not None and not resident_val:
+            raise ValueError("data.val_frame_budget sizes the groups of the resident validation: set data.resident_val: true, or drop the key")
         # the host module validates the keys, holds out the validation mapsets and keeps the validation loader
         self.host = LatentDataModule(batch_size, seq_len, num_workers, max_val_count, max_val_frac, data_path, shuffle_buffer_size, max_per_map,
                                      rank, world_size, max_len, pad_multiple, batch_frames, bucket_pool)
@@ -409,11 +514,20 @@ class ResidentLatentDataModule:
         self.feed = ResidentFeed(self.store, self.planner, self.ragged, rank)
         self._val_store: Optional[ResidentLatentStore] = None
         self._max_bytes = max_bytes
+        self.resident_val = bool(resident_val)
+        self._val_args = (val_batches, self.host.pad_multiple, val_frame_budget)
+        self.val_feed: Optional[ResidentLatentValFeed] = None
 
     def train_dataloader(self) -> ResidentFeed:
         return self.feed
 
     def val_dataloader(self):
+        if self.resident_val:
+            if self.val_feed is None:
+                # refused, before anything is allocated, if it does not fit under resident_max_gb beside the training store
+                val_store = ResidentLatentStore(self.host.val_set.mapsets, self.device, max_bytes=self._max_bytes, reserved_bytes=self.store.nbytes)
+                self.val_feed = ResidentLatentValFeed(val_store, *self._val_args)
+            return self.val_feed
         if self.store.has_frames:
             return self.host.val_dataloader()
         return self._style_val()

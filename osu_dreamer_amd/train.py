@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .data import RaggedLatentValBatch
 from .lr_schedule import LRScheduleArgs, make_lr_schedule
 from .model import DiffusionModel, DiffusionModelArgs, _coerce_args, valid_frames, zero_padding
 from .optim import FusedAdamWEMA
@@ -28,6 +29,7 @@ except Exception:  # pragma: no cover
     HAVE_LIGHTNING = False
 
 NUM_LABELS = 5   # osu_dreamer/data/beatmap/encode.py:50
+VAL_LOG_NAMES = ("loss", "osl", "del", "u_mape")     # od_loss_finalize's four outputs, in its order
 
 
 def frame_dist_sq(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -153,7 +155,10 @@ class DiffusionTrainer(_Base):
         self.diffusion_ema.update_parameters(self.diffusion)
 
     def validation_step(self, batch, batch_idx, *args, t=None, x0=None, **kwargs):
-        """train.py:128-139.  `t` / `x0` (keyword-only, not in the reference's signature) pin the noise for parity tests."""
+        """train.py:128-139.  `t` / `x0` (keyword-only, not in the reference's signature) pin the noise for parity tests.
+        A data.RaggedLatentValBatch (G held-out maps, already cut into their val_batches segments) goes to _validation_group."""
+        if isinstance(batch, RaggedLatentValBatch):
+            return self._validation_group(batch, t=t, x0=x0)
         h, z, s, l = batch
         with torch.no_grad():
             vb = self.val_batches
@@ -168,6 +173,78 @@ class DiffusionTrainer(_Base):
         self._log({f"val/{k}": v for k, v in log_dict.items()})
         return log_dict
 
+    def _validation_group(self, batch: RaggedLatentValBatch, *, t=None, x0=None) -> Dict[str, torch.Tensor]:
+        """validation_step on every map of the group at once: row offs[g] + j of the batch is segment j of map g, as validation_step cuts
+        it, so one ragged no-grad forward over the R = G * val_batches rows replaces G of them, and od_loss_finalize_groups reduces each
+        map's rows as od_loss_finalize reduces that map's own step.  `t` is stratified per map, as the per-map step's draw over its
+        val_batches rows.  Returns name -> (G,) device tensor, the maps in the group's order; nothing here reads the device."""
+        h, z, s = batch.h, batch.z, batch.s
+        vb, G, R = self.val_batches, s.size(0), z.size(0)
+        offs = [int(o) for o in batch.offs]
+        if offs != list(range(0, R + 1, vb)) or len(offs) != G + 1:
+            raise ValueError(f"the group's maps must hold val_batches = {vb} rows each: {G} maps, {R} rows, offs {offs}")
+        lens = [int(n) for n in batch.lengths]
+        dev = z.device
+        with torch.no_grad():
+            if t is None:
+                strata = torch.rand(G, vb, device=dev).argsort(1)          # a permutation of 0 .. vb-1 per map
+                u01 = ((strata + torch.rand(G, vb, device=dev)) / vb).reshape(R)
+                t = torch.special.ndtri(u01.clamp(1e-6, 1 - 1e-6)).sigmoid().to(torch.float32)
+            if x0 is None:
+                x0 = torch.randn_like(z, dtype=torch.float32)
+            # (the model does not read the labels, as in forward)
+            out, _ = _loss_forward(self.diffusion_ema.module, self.osl_weight, self.del_weight, False, lens, h, z,
+                                   s.repeat_interleave(vb, 0), t, x0, offs=offs)
+        self._log({f"val/{k}": v for k, v in zip(VAL_LOG_NAMES, out.mean(0).unbind(0))})
+        return dict(zip(VAL_LOG_NAMES, out.t().unbind(0)))
+
+
+def _loss_forward(model: DiffusionModel, osl_w, del_w, needs_grad, lens, h, x1, s, t, x0, offs=None):
+    """xt = lerp(x0, x1, t) -> denoiser forward -> the loss sums and their gradient wrt (u, v), all HIP kernels, then the reduction:
+    `offs` None — od_loss_finalize over the batch: (out (4,) = loss, osl, del, u_mape, and s as the engine read it), du written for the
+    backward; `offs` (G + 1 host ints, no-grad only) — od_loss_finalize_groups: out (G, 4), one row per map of rows [offs[g], offs[g+1])."""
+    f = model._f32c
+    h, x1, s, t, x0 = f(h), f(x1), f(s), f(t), f(x0)
+    B, E, L = x1.shape
+    dev = x1.device
+    if h.shape[0] == 1 and B > 1:
+        h = h.expand(B, -1, -1).contiguous()
+    eng, dt = model.engine, model._dtype()
+    eng.pack_weights(dt, train=needs_grad)
+    eng.plan(B, L, h.shape[0], dt, train=needs_grad, lens=lens)
+    xt = eng.buf("loss.xt", (B, E, L), torch.float32)
+    dsq = eng.buf("loss.dsq", (B,), torch.float32)
+    sums = eng.buf("loss.sums", (B, 3), torch.float32)
+    u = eng.buf("loss.u", (B,), torch.float32)
+    v = eng.buf("loss.v", (B, E, L), torch.float32)
+    dv = eng.buf("loss.dv", (B, E, L), torch.float32)
+    du = eng.buf("loss.du", (B,), torch.float32)
+    dsq.zero_()
+    sums.zero_()
+    if lens is not None:
+        # ragged: the audio's padding is read by real GEMMs and must be finite — it is zero-filled here, whatever the batch holds there;
+        # x0's and x1's padding is never read (od_make_xt_varlen / od_loss_grad_varlen select by frame)
+        h = zero_padding(h, valid_frames(lens, L, dev))
+        lens_d = eng.ws.t["vl.lens"]
+        ops.make_xt_varlen(x0, x1, t, xt, dsq, lens_d)
+    else:
+        ops.make_xt(x0, x1, t, xt, dsq)
+    eng.conditioning(h, s)
+    eng.pred(xt, u, v)
+    out = torch.empty(4 if offs is None else (len(offs) - 1, 4), dtype=torch.float32, device=dev)
+    eng._det_flush(dsq)                              # (OD_DETERMINISTIC: make_xt's per-sample sums, read by loss_grad)
+    if lens is not None:
+        ops.loss_grad_varlen(xt, x1, u, v, dsq, dv, sums, lens_d, model.c0, osl_w, del_w)
+    else:
+        ops.loss_grad(xt, x1, u, v, dsq, dv, sums, model.c0, osl_w, del_w)
+    eng._det_flush(sums)
+    if offs is None:
+        ops.loss_finalize(sums, dsq, u, out, du, model.c0, osl_w, del_w)
+    else:
+        assert not needs_grad and int(offs[-1]) == B, "per-map means are validation's: no du, and the maps cover the batch's rows"
+        ops.loss_finalize_groups(sums, dsq, u, offs, out, model.c0, osl_w, del_w)
+    return out, s
+
 
 class _TrainLossFn(torch.autograd.Function):
     """forward: xt = lerp(x0,x1,t) -> denoiser forward -> loss and its gradient wrt (u, v)
@@ -175,42 +252,7 @@ class _TrainLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model: DiffusionModel, osl_w, del_w, needs_grad, lens, h, x1, s, t, x0, *params):
-        f = model._f32c
-        h, x1, s, t, x0 = f(h), f(x1), f(s), f(t), f(x0)
-        B, E, L = x1.shape
-        dev = x1.device
-        if h.shape[0] == 1 and B > 1:
-            h = h.expand(B, -1, -1).contiguous()
-        eng, dt = model.engine, model._dtype()
-        eng.pack_weights(dt, train=needs_grad)
-        eng.plan(B, L, h.shape[0], dt, train=needs_grad, lens=lens)
-        xt = eng.buf("loss.xt", (B, E, L), torch.float32)
-        dsq = eng.buf("loss.dsq", (B,), torch.float32)
-        sums = eng.buf("loss.sums", (B, 3), torch.float32)
-        u = eng.buf("loss.u", (B,), torch.float32)
-        v = eng.buf("loss.v", (B, E, L), torch.float32)
-        dv = eng.buf("loss.dv", (B, E, L), torch.float32)
-        du = eng.buf("loss.du", (B,), torch.float32)
-        dsq.zero_()
-        sums.zero_()
-        if lens is not None:
-            # ragged: the audio's padding is read by real GEMMs and must be finite — it is zero-filled here, whatever the batch holds there;
-            # x0's and x1's padding is never read (od_make_xt_varlen / od_loss_grad_varlen select by frame)
-            h = zero_padding(h, valid_frames(lens, L, dev))
-            lens_d = eng.ws.t["vl.lens"]
-            ops.make_xt_varlen(x0, x1, t, xt, dsq, lens_d)
-        else:
-            ops.make_xt(x0, x1, t, xt, dsq)
-        eng.conditioning(h, s)
-        eng.pred(xt, u, v)
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        eng._det_flush(dsq)                              # (OD_DETERMINISTIC: make_xt's per-sample sums, read by loss_grad)
-        if lens is not None:
-            ops.loss_grad_varlen(xt, x1, u, v, dsq, dv, sums, lens_d, model.c0, osl_w, del_w)
-        else:
-            ops.loss_grad(xt, x1, u, v, dsq, dv, sums, model.c0, osl_w, del_w)
-        eng._det_flush(sums)
-        ops.loss_finalize(sums, dsq, u, out, du, model.c0, osl_w, del_w)
+        out, s = _loss_forward(model, osl_w, del_w, needs_grad, lens, h, x1, s, t, x0)
         ctx.model, ctx.style, ctx.nparams = model, s, len(params)
         return out[0], out[1], out[2], out[3]
 
